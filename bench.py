@@ -14,7 +14,19 @@ N > 1: pure data parallel, weak scaling (bs 32 per GPU), RCCL all-reduce of the 
 gradient arenas; the generator's backward runs in buckets (swn_model_backward_G_part) and each
 bucket's all-reduce overlaps the back-propagation of the earlier layers.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps, writes the outputs of
+the last timed step if --dump-outputs is given, and prints the line: nothing else runs on the GPU or the host.
+--dump-outputs DIR writes what a caller of the timed step receives after its last step as DIR/<name>.npy:
+`loss_<name>` (float64 scalars, every slot of the library's loss table), `output` (the generator's fakes of that
+step) and `weights_<net>` (every parameter of the net after the step's update, flattened in state_dict order and
+concatenated), float32; an array above its share of the 64 MB limit is written as a fixed, seeded sample of its
+elements (the same indices in every run).  The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
+
+--full additionally measures, after the timed steps and the dump (on the same model), what earlier lines carried;
+--no-roofline / --no-cpu-baseline leave parts of it out:
+  config.routing -- digest of the launch list of one further step (swn_route_trace).
+  dp_buckets   -- N > 1 (or the phased / 1-rank RCCL forms): back-propagation time and bytes of each exchange bucket.
   roofline     -- dominant kernel family: FLOPs the kernel EXECUTES (2*M*N*K per launch) / HIP-event time of
                   those launches (`achieved`, fp32-equivalent TFLOP/s) vs `peak` = the nominal dense fp16 MFMA peak
                   (2500 TFLOP/s) / the 16-bit MFMA products the kernel issues per fp32 product (3 in the two-plane
@@ -29,15 +41,18 @@ Prints ONE JSON line (rank 0).  Extra objects:
                   step_frac_executed by exactly that factor and is NOT a utilisation figure.
                   `traffic` = HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC
                   passes of this same command (`traffic_source`), not collected inside this run.
+                  `exact_f32_form` (warp stage, N = 1, f32): the same step built under SWN_SPLIT=0.
   cpu_baseline -- the CPU oracle (a port of the reference step, oracle/swapnet_oracle.py) timed
                   on this box's host cores on a bounded sample (N=1 only).
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.abspath(__file__))
@@ -75,6 +90,65 @@ def mfma16_per_product(kernel_name):
     if "_dma_" in kernel_name:
         return 6
     return 0
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6          # --dump-outputs: all files of one run together
+
+
+def _seeded_indices(n, cap, seed):
+    """Sorted sample of `cap` element indices out of `n` (None: keep all), the same for the same (n, cap, seed)."""
+    if n <= cap:
+        return None
+    return torch.randint(n, (cap,), generator=torch.Generator().manual_seed(seed)).sort().values
+
+
+def _sampled(t, cap, seed):
+    idx = _seeded_indices(t.numel(), cap, seed)
+    if idx is None:
+        return t.detach().float().cpu().numpy()
+    return t.detach().reshape(-1)[idx.to(t.device)].float().cpu().numpy()
+
+
+def _sampled_params(model, net, cap, seed):
+    """Every parameter of `net` flattened in state_dict order and concatenated (independent of the library's arena layout);
+    above `cap` elements, a seeded sample of the concatenation, fetched parameter by parameter."""
+    infos = model.param_infos(net)
+    total = sum(math.prod(sh) for sh in infos.values())
+    idx = _seeded_indices(total, cap, seed)
+    parts, off = [], 0
+    for name, shape in infos.items():
+        n = math.prod(shape)
+        t = model.get_param(net, name, shape).reshape(-1)
+        if idx is None:
+            parts.append(t.cpu())
+        else:
+            lo, hi = int(torch.searchsorted(idx, off)), int(torch.searchsorted(idx, off + n))
+            if hi > lo:
+                parts.append(t[(idx[lo:hi] - off).to(t.device)].cpu())
+        off += n
+    return torch.cat(parts).float().numpy()
+
+
+def model_outputs(model, engine, nets, prefix="", output_cap=4 << 20, weight_cap=6 << 20):
+    """What a caller of NativeModel.step receives after the step: the loss table, the generator's output and the updated
+    weights of the trained nets."""
+    out = {f"{prefix}loss_{k}": np.float64(v) for k, v in model.losses().items()}
+    out[f"{prefix}output"] = _sampled(model.output(), output_cap, seed=11)
+    for net in nets:
+        tag = {engine.NET_G: "G", engine.NET_D: "D"}[net]
+        out[f"{prefix}weights_{tag}"] = _sampled_params(model, net, weight_cap, seed=12 + net)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: (a if a.dtype == np.float64 else a.astype(np.float32)) for k, a in arrays.items()}
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {size} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def cpu_baseline(sample_bs=4, size=256, warm=2, timed=5):
@@ -180,6 +254,8 @@ def bench_infer(args):
         lat.sort()
         res[mode] = {"p50_ms": round(lat[len(lat) // 2], 4), "p90_ms": round(lat[int(len(lat) * 0.9)], 4),
                      "min_ms": round(lat[0], 4)}
+    if args.dump_outputs:              # the warp stage's label map and the texture stage's output of the last replay
+        dump_outputs(args.dump_outputs, {"labels": pipe.labels().float().cpu().numpy(), "output": tex.output().float().cpu().numpy()})
     out = {"metric": "two-stage inference latency (warp -> texture), 256x256, batch 1", "value": res["hipgraph"]["p50_ms"],
            "unit": "ms/image (p50)", "n_gpus": 1, "steps": max(args.steps, 50), "warmup": max(args.warmup, 2),
            "ms_per_step": res["hipgraph"]["p50_ms"], "higher_is_better": False, "scaling": "n/a", "vs_baseline": None,
@@ -231,6 +307,10 @@ def bench_joint(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ms = dt / args.steps * 1e3
+    if args.dump_outputs:
+        arrays = model_outputs(warp, engine, (engine.NET_G, engine.NET_D), "warp_", output_cap=2 << 20, weight_cap=5 << 19)
+        arrays.update(model_outputs(tex, engine, (engine.NET_G, engine.NET_D), "texture_", output_cap=2 << 20, weight_cap=5 << 19))
+        dump_outputs(args.dump_outputs, arrays)
     lw, lt = warp.losses(), tex.losses()
     out = {"metric": f"images/sec, joint warp + texture G+D steps (both GAN pairs in one process), {H}x{W} / {S}x{S}, bs={B}/GPU",
            "value": round(B * args.steps / dt, 3), "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -329,8 +409,13 @@ def main():
     ap.add_argument("--captured", action="store_true",
                     help="run the step as a recorded hipGraph (swn_model_step_captured, BASELINE.json C5's captured step); "
                          "N = 1 only, bit-identical results")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, sustained MFMA rate, routing digest, exact-fp32 form, "
+                         "per-bucket exchange timings and the CPU baseline (a plain run measures only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline and routing passes out")
     ap.add_argument("--with-h2d", action="store_true",
                     help="additionally time steps that re-upload the batch from host memory every step through "
                          "the model API (set_input + step), reported as `h2d_inclusive` (never `value`)")
@@ -444,6 +529,8 @@ def main():
         gathered = [None] * world
         dist.all_gather_object(gathered, mine)
     losses = model.losses()
+    if args.dump_outputs and rank == 0:          # before anything --full runs on the same model
+        dump_outputs(args.dump_outputs, model_outputs(model, engine, (engine.NET_G, engine.NET_D)))
     ms = dt / args.steps * 1e3
     ips = world * B * args.steps / dt
     flop_per_img = (217.8 if texture else GFLOP_PER_IMG_256) * 1e9 * (S * S) / (256 * 256)
@@ -488,7 +575,7 @@ def main():
 
     if world > 1:
         out["ranks"] = [{"rank": r, "device": d} for r, d in gathered]
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # HIP events around every implicit-GEMM launch, on the stream they are launched on.  The timed region
         # above runs weight-gradient work on the library's second stream, where a kernel's wall time includes
         # whatever shares the GPU with it; for per-kernel durations this pass keeps everything in order on one
@@ -623,7 +710,7 @@ def main():
         if sus["random_operands"]["fp16_tflops"] > 0 and per_product:
             r["sustained"]["fp32_equivalent_tflops"] = round(sus["random_operands"]["fp16_tflops"] / per_product, 1)
             r["frac_of_sustained"] = round(r["achieved"] * per_product / sus["random_operands"]["fp16_tflops"], 4)
-    if rank == 0 and (world > 1 or os.environ.get("SWAPNET_BENCH_PHASED") or rccl1):
+    if rank == 0 and args.full and (world > 1 or os.environ.get("SWAPNET_BENCH_PHASED") or rccl1):
         # measured back-propagation time and gradient bytes of each exchange bucket (what engine.cpp's bucket boundaries are
         # sized on): HIP events around swn_model_backward_G_part, no exchange in between
         lab = draw_labels()
@@ -673,7 +760,7 @@ def main():
         res["h2d_bytes_per_step"] = {"onehot_fp32": sum(t.numel() * 4 for t in host),
                                      "label_maps": host[0].numel() * 4 + sum(t.numel() * 4 for t in labels)}
         out["h2d_inclusive"] = res
-    if rank == 0 and not args.no_roofline:      # (the PMC passes of profiles/ run with --no-roofline: exactly the timed steps)
+    if rank == 0 and args.full and not args.no_roofline:      # (the PMC passes of profiles/ run with --no-roofline: exactly the timed steps)
         # which kernel every layer launched (swn_route_trace): the digest the parity tests compare their own runs with
         # (tests/backends.py assert_default_routing), and the switches that were set in this process
         import hashlib
@@ -688,7 +775,7 @@ def main():
                                     "switches": sorted(k + "=" + v for k, v in os.environ.items() if k.startswith("SWN_"))}
     if rank == 0 and world == 1 and "roofline" in out and not texture and SPLIT and args.precision == "f32" and not args.captured:
         out["roofline"]["exact_f32_form"] = exact_f32_form(ctx, model, engine, batch, B, S, draw_labels)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_texture() if texture else cpu_baseline()
     # the JSON line is the LAST thing on stdout: RCCL writes its version banner through C stdio, which (not a tty) sits in a
     # buffer until the process exits -- flush it, and tear the process group down, before printing

@@ -53,7 +53,7 @@ def store_full(out, key, t, stride=1):
     if stride > 1:
         t = t[..., ::stride, ::stride].contiguous()
         out[key + "/stride"] = np.int64(stride)
-    out[key + "/full"] = t.numpy()
+    out[key + "/full"] = t.numpy().copy()       # a snapshot: parameters are updated in place by the next step
 
 
 def compare_full(gold, key, t, rtol=1e-3, flip_slices=0, flip_cap=1e-2, outlier_frac=0.0):

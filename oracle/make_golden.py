@@ -97,10 +97,10 @@ def golden_roi_ops(path, seed=11):
     print("wrote", path)
 
 
-def golden_warp(path, H=64, B=2, init_seed=0, step_seeds=(100, 101), full="warp"):
+def golden_warp(path, H=64, B=2, init_seed=0, step_seeds=(100, 101), full="warp", keep=None):
     """Steps of the REAL WarpModel (models/warp_model.py:106-183 under models/base_gan.py:194-203).  full = which FULL_TENSORS set is
     stored whole: "warp" (64 x 64, bs 2), "warp_256" (BASELINE.json C2's resolution: 256 x 256, the resblocks on 16 x 16 maps, PatchGAN on
-    31 x 31 -- fakes at stride 4), "warp_c1" (C1: 64 x 64, bs 4)."""
+    31 x 31 -- fakes at stride 4), "warp_c1" (C1: 64 x 64, bs 4).  keep = key prefixes written (None: all)."""
     from oracle.swapnet_oracle import synth_warp_batch
     from models.warp_model import WarpModel
     from oracle.golden_io import FULL_STRIDE
@@ -168,6 +168,8 @@ def golden_warp(path, H=64, B=2, init_seed=0, step_seeds=(100, 101), full="warp"
     out["meta/init_seed"] = np.int64(init_seed)
     out["meta/step_seeds"] = np.array(step_seeds, dtype=np.int64)
     out["meta/torch"] = np.array(torch.__version__)
+    if keep:
+        out = OrderedDict((k, v) for k, v in out.items() if k.startswith(keep))
     np.savez_compressed(path, **out)
     print("wrote", path, len(out), "entries")
 
@@ -492,10 +494,12 @@ if __name__ == "__main__":
         golden_texture(os.path.join(gold, "texture_step_64.npz"))
     if "warp256" in which:          # BASELINE.json C2's resolution (bs 2: seconds on the CPU)
         golden_warp(os.path.join(gold, "warp_step_256.npz"), H=256, B=2, step_seeds=(100,), full="warp_256")
+        # its second step in a file of its own (both steps in one file make too large a fixture); tests/test_oracle_golden.py merges them
+        golden_warp(os.path.join(gold, "warp_step_256_step1.npz"), H=256, B=2, step_seeds=(100, 101), full="warp_256", keep=("step1/", "meta/"))
     if "warp_c1" in which:          # BASELINE.json C1: 64 x 64, bs 4
         golden_warp(os.path.join(gold, "warp_step_c1.npz"), H=64, B=4, step_seeds=(100, 101), full="warp_c1")
     if "texture256" in which:       # BASELINE.json C3's resolution: the depth-8 U-Net, 12 ROIs incl. a degenerate box
-        golden_texture(os.path.join(gold, "texture_step_256.npz"), H=256, B=1, step_seeds=(200,), full="texture_256")
+        golden_texture(os.path.join(gold, "texture_step_256.npz"), H=256, B=1, step_seeds=(200, 201), full="texture_256")
     if "roi" in which:
         golden_roi(os.path.join(gold, "notebook_rois.npz"))
     if "modes" in which:

@@ -33,7 +33,7 @@ timeout 420 python -m pytest -m gpu -q -x \
 tail -15 $O/t_unverified.log
 unset SWAPNET_UNVERIFIED_GPU
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $?" | tee -a $O/rc.txt
-timeout 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/rc.txt
+timeout 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/rc.txt
 tail -c 600 $O/bench_default.json
 timeout 200 python bench.py --stage joint --steps 10 --warmup 3 > $O/bench_joint.json 2> $O/bench_joint.err; echo "bench joint rc $?" | tee -a $O/rc.txt
 tail -c 400 $O/bench_joint.json

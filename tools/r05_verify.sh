@@ -13,7 +13,7 @@ timeout 900 python -m pytest -m gpu -q --durations=15 \
   > $O/tests.log 2>&1; echo "tests rc $?" | tee -a $O/rc.txt
 tail -30 $O/tests.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $?" | tee -a $O/rc.txt
-timeout 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/rc.txt
+timeout 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/rc.txt
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r05verify/bench_default.json').read().strip().splitlines()[-1])

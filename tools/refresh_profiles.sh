@@ -9,15 +9,15 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 --with-h2d > $O/bench_c2.json 2> $O/bench_c2.err
+python bench.py --full --steps 20 --warmup 5 --with-h2d > $O/bench_c2.json 2> $O/bench_c2.err
 python -c "import json;d=json.load(open('$O/bench_c2.json'));print(d['value'],d['ms_per_step'],d['roofline']['achieved'],d['roofline']['frac'],d['roofline']['pipe_util_nominal_step'],d.get('cpu_baseline'))"
-python bench.py --stage texture --steps 12 --warmup 4 > $O/bench_c3.json 2> $O/bench_c3.err
-python bench.py --precision f16 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_c2_f16.json 2> $O/bench_c2_f16.err
+python bench.py --full --stage texture --steps 12 --warmup 4 > $O/bench_c3.json 2> $O/bench_c3.err
+python bench.py --full --precision f16 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_c2_f16.json 2> $O/bench_c2_f16.err
 python bench.py --captured --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_c2_captured.json 2> $O/bench_c2_captured.err
 python bench.py --stage infer > $O/bench_infer.json 2> $O/bench_infer.err
 python bench.py --stage joint --steps 12 --warmup 4 > $O/bench_joint.json 2> $O/bench_joint.err
 python bench.py --stage joint --captured --steps 12 --warmup 4 > $O/bench_joint_captured.json 2> $O/bench_joint_captured.err
-SWAPNET_BENCH_RCCL1=1 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $O/bench_c2_rccl_world1.json 2> $O/bench_c2_rccl_world1.err
+SWAPNET_BENCH_RCCL1=1 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $O/bench_c2_rccl_world1.json 2> $O/bench_c2_rccl_world1.err
 # same-box A/B of this round's switches (ms/step)
 for V in X=default SWN_CONV_STATS=0 SWN_TAIL_SPLIT=0 SWN_PAIR=0 SWN_AMAX_FUSED=0 SWN_PREFETCH=0 SWN_STREAM_ADAMW=0 SWN_OVERLAP=0 X=default2; do
   env $V python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-roofline 2> /dev/null | python -c "import sys,json;d=json.loads(sys.stdin.read());print('$V', d['ms_per_step'], d['value'])" >> $O/ab_switches.txt
