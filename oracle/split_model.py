@@ -64,3 +64,35 @@ def planes_bf16(x):
 def matmul_three_plane(a, b):
     ah, am, al = planes_bf16(a); bh, bm, bl = planes_bf16(b)
     return ((al @ bh + ah @ bl) + am @ bm) + ((am @ bh + ah @ bm) + ah @ bh)
+
+
+def matmul_one_plane(a, b, ka=None, kb=None, truncate=False):
+    """C = A @ B the way the one-plane configuration forms it (SWN_PC_PLANES=1 / SWN_WGRAD_PLANES=1, bench.py --precision f16:
+    conv_gemm.hip split8h1 and conv_precut_kernel with one plane): each operand ONE fp16 value of x * 2^k, rounded to nearest, one
+    MFMA per product, fp32 accumulation.  `truncate` cuts toward zero instead (what the test of the bias must reject).
+
+    Error per output element.  u = 2^-11 is fp16's unit round-off.  A scaled element x' = x 2^k is either normal (|x'| >= 2^-14:
+    |fl(x') - x'| <= u |x'|) or subnormal (spacing 2^-24: |fl(x') - x'| <= 2^-25).  With amax 2^k >= 2^(top-1), 2^-k <= amax 2^(1-top),
+    so per element  |da| <= u |a| + e_a,  e_a = amax_a 2^-(24 + top_a)   (top_a = PC_TOP_A = 12: amax 2^-36; weights, PC_TOP_B = 10:
+    amax 2^-34).  A product a'b' - ab = da b + a db + da db, so summed over k
+        |err| <= (2u + u^2) conv(|a|,|b|) + (1 + u) (e_a conv(1,|b|) + e_b conv(|a|,1)) + e_a e_b conv(1,1) + fp32 accumulation,
+    the last below K 2^-24 conv(|a|,|b|) <= 2^-10 conv(|a|,|b|) for K <= 2^14.  The tests hold
+        |err| <= 2 (2^-10 conv(|a|,|b|) + e_a conv(1,|b|) + e_b conv(|a|,1))
+    per element: the factor 2 covers the u^2, (1 + u) and e_a e_b terms and the accumulation."""
+    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
+    ka = scale_exp(np.abs(a).max(), PC_TOP_A) if ka is None else ka
+    kb = scale_exp(np.abs(b).max(), PC_TOP_B) if kb is None else kb
+
+    def cut(x, k):
+        xs = (x * np.float32(2.0) ** np.float32(k)).astype(np.float32)
+        return (_trunc_fp16(xs) if truncate else xs.astype(np.float16)).astype(np.float32)
+
+    acc = cut(a, ka) @ cut(b, kb)
+    return (acc * np.float32(2.0) ** np.float32(-ka)) * np.float32(2.0) ** np.float32(-kb)
+
+
+def one_plane_bound(a, b, top_a=PC_TOP_A, top_b=PC_TOP_B):
+    """The per-element bound of matmul_one_plane (twice the analytic one; see there), float64."""
+    A, B = np.abs(np.asarray(a, np.float64)), np.abs(np.asarray(b, np.float64))
+    ea, eb = A.max() * 2.0 ** -(24 + top_a), B.max() * 2.0 ** -(24 + top_b)
+    return 2.0 * (2.0 ** -10 * (A @ B) + ea * (np.ones_like(A) @ B) + eb * (A @ np.ones_like(B)))

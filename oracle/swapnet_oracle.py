@@ -839,12 +839,14 @@ class WarpStepOracle:
     def astype(self, dtype):
         return _clone_step_oracle(self, dtype)
 
-    def step(self, bodys, inputs, targets, labels=None):
+    def step(self, bodys, inputs, targets, labels=None, targets_G=None):
         """optimize_parameters (base_gan.py:194-203; warp_model.py:106-167).
         `labels` = the three smooth-label scalars (fake_D, real_D, real_G); drawn
-        from the global CPU RNG in the reference's order when None."""
+        from the global CPU RNG in the reference's order when None.  `targets_G`: other targets for
+        backward_G's cross-entropy term than backward_D saw (a phased caller that sets new targets in between)."""
         h = self.h
         bodys, inputs, targets = bodys.to(self.dtype), inputs.to(self.dtype), targets.to(self.dtype)
+        targets_G = targets if targets_G is None else targets_G.to(self.dtype)
         G, D = _leaf(self.G), _leaf(self.D)
         rp, B = self.patterns, bodys.shape[0]
         with _pscope(rp, "G"):
@@ -885,7 +887,7 @@ class WarpStepOracle:
         self.optD.apply(self.D, self.grads_D)                                          # base_gan.py:199
         # ---- backward_G (warp_model.py:141-167) with the UPDATED D
         D2 = OrderedDict((k, v.detach()) for k, v in self.D.items())
-        loss_ce = F.cross_entropy(fakes, torch.argmax(targets, dim=1)) * h["lambda_ce"]
+        loss_ce = F.cross_entropy(fakes, torch.argmax(targets_G, dim=1)) * h["lambda_ce"]
         with _pscope(rp, "D_G"):
             pred = patchgan_forward(D2, torch.cat((bodys, fakes), 1))
         l_g = draw(2)

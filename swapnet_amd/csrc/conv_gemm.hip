@@ -2639,8 +2639,11 @@ void conv_force_naive(int on) { g_force_naive = on; }
 // SWN_AMAX_FUSED=0: every launch takes the amax of its operands itself (A/B against the producer-side slots; read per launch)
 static bool amax_fused_on() { return !(getenv("SWN_AMAX_FUSED") && atoi(getenv("SWN_AMAX_FUSED")) == 0); }
 // ---- pre-cut ring kernel: schedule + launch ------------------------------------------------------------------------
+// SWN_PRECUT=0: no pre-cut ring kernel.  Read ONCE per process, here and by conv_precut_tile alike: the engine decides at build time
+// which weight operands exist only in pre-cut form, and a launch that changed its mind later would run a fall-back on operands
+// prepared for the pre-cut kernel (or fail at a model's epilogue statistics)
 static bool pc_on() {
-  const bool on = !(getenv("SWN_PRECUT") && atoi(getenv("SWN_PRECUT")) == 0);      // read per launch (tests / A-B runs)
+  static const bool on = !(getenv("SWN_PRECUT") && atoi(getenv("SWN_PRECUT")) == 0);
   return on;
 }
 // 2 (default): two fp16 planes per operand, three MFMAs per product; 1: the reduced-precision configuration (one fp16 plane per
@@ -2752,8 +2755,7 @@ int conv_fwd_stat_chunk(int xC, int Npad, int HoWo, int nimg, int K) {
   return 128;
 }
 int conv_precut_tile(int xC, int Npad) {
-  static const bool off = getenv("SWN_PRECUT") && atoi(getenv("SWN_PRECUT")) == 0;
-  if (off || g_force_naive || !dma_on() || !split_on() || xC % 16 || Npad <= 32) return 0;
+  if (!pc_on() || g_force_naive || !dma_on() || !split_on() || xC % 16 || Npad <= 32) return 0;
   return pc_tile_for(Npad);
 }
 size_t conv_precut_elems(int K, int Npad, int bn) {

@@ -271,6 +271,7 @@ class WarpModel final : public Model {
       if (!is_train) throw Error(1, "targets are only used in training");
       if (C != Cc) throw Error(1, "target_cloths must have " + std::to_string(Cc) + " channels");
       nchw_to_nhwc(s, src, N, C, H, W, Dx.batch(B, B).v.slice(0, Ccp));
+      ce_done_ = false;           // an early CE term was taken against the old targets: backward_G takes it again
     } else {
       throw Error(1, "set_input: unknown slot");
     }
@@ -279,7 +280,7 @@ class WarpModel final : public Model {
   void set_input_labels(int slot, const int32_t* lab, int N, int Hh, int Ww) override {
     if (N != B || Hh != H || Ww != W) throw Error(1, "set_input_labels: shape mismatch with the model's (B,H,W)");
     if (slot == 1) labels_to_onehot(ctx->s, lab, cloth.v, Cc);
-    else if (slot == 2 && is_train) labels_to_onehot(ctx->s, lab, Dx.batch(B, B).v.slice(0, Ccp), Cc);
+    else if (slot == 2 && is_train) { labels_to_onehot(ctx->s, lab, Dx.batch(B, B).v.slice(0, Ccp), Cc); ce_done_ = false; }
     else throw Error(1, "set_input_labels: slot has no label form");
     refresh_input_slots(slot);
   }

@@ -66,3 +66,31 @@ def test_one_signed_operands_carry_no_bias_beyond_fp32():
     bias = float(np.mean((c - ref) / ref))
     print("one-signed K=9216: rel-L2 %.2e, mean relative bias %.2e" % (_err(c, a, b), bias))
     assert _err(c, a, b) < 4e-7 and abs(bias) < 2e-7          # GPU test_ops: 1.36e-7, bias -3.5e-8
+
+
+def test_one_plane_form_element_bound():
+    """The one-plane configuration (bench.py --precision f16): every element of A @ B within
+    2 (2^-10 |A||B| + amax_A 2^-36 1|B| + amax_B 2^-34 |A|1) of float64 (oracle/split_model.py matmul_one_plane derives it), on
+    heavy-tailed operands with ONE outlier 2^18 x the bulk in each; and on one-signed operands (post-ReLU activations against a
+    positive filter) round-to-nearest leaves no mean relative bias beyond 2^-12 -- a truncating cut does, and fails the same check."""
+    rng = np.random.default_rng(17)
+    a = rng.normal(size=(96, 2048)).astype(np.float32)
+    b = (rng.normal(size=(2048, 64)) * 0.03).astype(np.float32)
+    a[5, 700] = 2.0 ** 18
+    b[1200, 3] = -(2.0 ** 18) * 0.03
+    for what, (x, y) in (("outliers", (a, b)), ("bulk", (a[:, :700], b[:700]))):
+        c = S.matmul_one_plane(x, y)
+        err = np.abs(c - x.astype(np.float64) @ y.astype(np.float64))
+        worst = float((err / S.one_plane_bound(x, y)).max())
+        print("one plane, %s: worst |err| / bound %.3f" % (what, worst))
+        assert worst <= 1.0, (what, worst)
+    assert _err(S.matmul_one_plane(a, b), a, b) > 1e-5        # (11-bit operands: two orders of magnitude above the two-plane form)
+    xp = np.abs(rng.normal(size=(64, 4608))).astype(np.float32)
+    yp = np.abs(rng.normal(size=(4608, 32)) * 0.02).astype(np.float32)
+    ref = xp.astype(np.float64) @ yp.astype(np.float64)
+    bias_rn = float(np.mean((S.matmul_one_plane(xp, yp) - ref) / ref))
+    bias_tr = float(np.mean((S.matmul_one_plane(xp, yp, truncate=True) - ref) / ref))
+    print("one-signed K=4608: mean relative bias, nearest %+.2e, truncating %+.2e" % (bias_rn, bias_tr))
+    assert abs(bias_rn) < 2.0 ** -12, bias_rn
+    assert abs(bias_tr) > 2.0 ** -12, bias_tr                   # (the check would catch a truncating cut)
+    assert float((np.abs(S.matmul_one_plane(xp, yp) - ref) / S.one_plane_bound(xp, yp)).max()) <= 1.0
