@@ -73,7 +73,7 @@ int swn_ctx_create(int device, void* hip_stream, int create_stream, size_t works
     h->box->c = std::make_unique<Ctx>(st, workspace_bytes);
     h->c = h->box->c.get();
     h->c->device_index = device;
-    if (!(getenv("SWN_OVERLAP") && atoi(getenv("SWN_OVERLAP")) == 0)) h->c->enable_side(device);
+    if (env_on(getenv("SWN_OVERLAP"))) h->c->enable_side(device);
     *out = h.release();
   });
 }

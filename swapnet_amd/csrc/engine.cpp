@@ -238,7 +238,7 @@ size_t Net::reserve_dg(Op* op, size_t elems) {
 namespace {
 struct ConvGeom {
   Gather fwd;       // forward gather (Ho,Wo filled)
-  int Ho, Wo;
+  int Ho = 0, Wo = 0;
 };
 ConvGeom conv_geom(ConvKind kind, int H, int W) {
   ConvGeom c;
@@ -255,47 +255,115 @@ ConvGeom conv_geom(ConvKind kind, int H, int W) {
   g.Ho = c.Ho; g.Wo = c.Wo;
   return c;
 }
-}  // namespace
 
+// The Winograd switches, read when a layer is built (tests toggle them between layers): Net::conv / Net::convT read them once
+// and hand them to the route predicates below
+struct WinoSwitches {
+  bool on, s2_on;       // SWN_WINOGRAD, SWN_WINO_S2: off when 0
+  int minc, force_m;    // SWN_WINO_MINC > 0: the channel threshold of every form (tests: small channel counts too); SWN_WINO_M
+};
+WinoSwitches wino_switches() {
+  return {env_on(getenv("SWN_WINOGRAD")), env_on(getenv("SWN_WINO_S2")), env_int(getenv("SWN_WINO_MINC"), 0), env_int(getenv("SWN_WINO_M"), 0)};
+}
 
 // ---- strided Winograd F(4x4, 2x2) for the k4 s2 p1 convolutions and their transposes (ops.h wino_s2_*, wino.hip) ----------
 // Used where the activation side dominates: the transformed filters are 6.25x the weights (per GEMM direction) and are
 // re-derived every optimizer step, so the 8-16 M-parameter layers at 4x4 / 8x8 maps stay on the direct kernels.
-namespace {
-bool s2_wino_wanted(int Cfine, int Ccoarse, int Hc, int Wc) {
-  const bool off = (getenv("SWN_WINOGRAD") && atoi(getenv("SWN_WINOGRAD")) == 0) ||       // read per layer built (tests toggle it)
-                   (getenv("SWN_WINO_S2") && atoi(getenv("SWN_WINO_S2")) == 0);
-  if (off) return false;
-  const int minc_env = getenv("SWN_WINO_MINC") ? atoi(getenv("SWN_WINO_MINC")) : 0;      // (tests: small channel counts too)
-  const int minc = minc_env > 0 ? minc_env : 256;
+bool s2_wino_wanted(const WinoSwitches& sw, int Cfine, int Ccoarse, int Hc, int Wc) {
+  if (!sw.on || !sw.s2_on) return false;
+  const int minc = sw.minc > 0 ? sw.minc : 256;
   if (Ccoarse < minc || Cfine < 32 || Cfine % 4 || Ccoarse % 16 || Hc < 2 || Wc < 2) return false;
   // coarse maps of at least 16 x 16: below that the GEMMs are a handful of tiles (nothing to gain), and the 8 x 8 ... 2 x 2
   // levels of the pix2pix U-Net sit in front of InstanceNorms over 64 ... 4 pixels, which amplify the (2.5x larger) round-off
   // of the Winograd form: with them on it, the texture generator's gradients were 1e-4 ... 3e-4 off the pinned float64 oracle,
   // without 6e-5 (tests/test_pattern_replay.py)
-  if (minc_env <= 0 && Hc * Wc < 256) return false;
+  if (sw.minc <= 0 && Hc * Wc < 256) return false;
   return (size_t)16 * Cfine * Ccoarse <= ((size_t)1 << 22);
 }
+
+// Stride-1 convs with MFMA-friendly channel counts run as Winograd F(m x m, r x r): transform,
+// (m+r-1)^2 batched GEMMs, inverse transform (wino.hip).  3x3: F(4x4,3x3) when H and W are
+// multiples of 4 (4x fewer multiplies), else F(2x2,3x3) (2.25x); PatchGAN's k4 s1: F(3x3,4x4) (4x).
+// ... when the channel counts are large enough for the GEMMs (K = Cin each) to run at MFMA speed
+// and to amortise the HBM-bound transforms: measured on VGG16 (texture C3), the 6-point forms win
+// from 64 channels up, F(2x2,3x3) (4x instead of 2.25x transform data per input) only from 256.
+// Returns m, 0 = the layer stays on the direct kernels.
+int wino_s1_m(const WinoSwitches& sw, ConvKind kind, int Cip, int Co, int H, int W) {
+  const bool is_k3 = kind == CK_K3S1_REFLECT || kind == CK_K3S1_ZERO, is_k4 = kind == CK_K4S1;
+  const int wm = is_k4 ? 3 : ((sw.force_m != 2 && H % 4 == 0 && W % 4 == 0) ? 4 : 2);
+  const int minc = sw.minc > 0 ? sw.minc : (wm == 2 ? 256 : 64);
+  const bool wino = sw.on && Cip % 32 == 0 && Co % 32 == 0 && Cip >= minc && Co >= minc && H >= 4 && W >= 4 &&
+                    ((is_k3 && H % 2 == 0 && W % 2 == 0) || is_k4);
+  return wino ? wm : 0;
+}
+
+// ---- the batched GEMMs over Winograd planes: P planes of T rows each ---------------------------------------------------------
 TView plane_mat(float* p, size_t T, int C) {
   TView v; v.p = p; v.N = 1; v.H = 1; v.W = (int)T; v.C = C; v.cs = C; return v;     // T x C matrix
 }
-}  // namespace
+// How a GEMM learns the scale of a plane operand: the exponent its producer stored it in pair form with (ops.h
+// wino_input_transform), or the planes' amax slot, or neither (fp32 planes without a slot: the launch takes the amax itself)
+struct PlaneScale { const int* pair_k = nullptr; const float* amax = nullptr; };
+PlaneScale plane_scale(bool pairs, const int* k, const float* amax) { return pairs ? PlaneScale{k, nullptr} : PlaneScale{nullptr, amax}; }
+// The [K x N] panels: fp32 (NULL where the panel exists only pre-cut) and / or pre-cut for column tile `tile` (0 = none), `bs`
+// elements between planes
+struct PlanePanel { const float* w; const uint16_t* pc; int tile; size_t bs; };
+// P planes of [T x K] . [K x N] -> [T x N]
+ConvFwdArgs plane_gemm(float* x, float* y, size_t T, int K, int N, int Cout, int P, PlaneScale xs, PlanePanel w) {
+  ConvFwdArgs g;
+  g.x = plane_mat(x, T, K); g.g.Ho = 1; g.g.Wo = (int)T;
+  g.w = w.w; g.Npad = N; g.Cout = Cout;
+  g.y = plane_mat(y, T, N);
+  g.batch = P; g.x_bs = T * K; g.w_bs = (size_t)K * N; g.y_bs = T * N;
+  g.x_pair_k = xs.pair_k; g.x_amax = xs.amax;
+  if (w.tile) { g.wpc = w.pc; g.wpc_bn = w.tile; g.wpc_bs = w.bs; }
+  return g;
+}
+// P planes of [T x K]^T . [T x N] -> [K x N]
+ConvWgradArgs plane_wgrad(float* x, float* dy, float* dw, size_t T, int K, int N, int Cout, int P, PlaneScale xs, PlaneScale dys) {
+  ConvWgradArgs g;
+  g.x = plane_mat(x, T, K); g.g.Ho = 1; g.g.Wo = (int)T;
+  g.dy = plane_mat(dy, T, N);
+  g.dw = dw; g.Npad = N; g.Cout = Cout;
+  g.batch = P; g.x_bs = T * K; g.dy_bs = T * N; g.dw_bs = (size_t)K * N;
+  g.x_pair_k = xs.pair_k; g.x_amax = xs.amax;
+  g.dy_pair_k = dys.pair_k; g.dy_amax = dys.amax;
+  return g;
+}
 
-// ---- Conv2d ---------------------------------------------------------------------------
-// y.v receives act(conv(x)+bias).  In backward y.g is the gradient w.r.t. that output.
 // Column tile of a pre-cut operand written by the 6-point FILTER TRANSFORM (ops.h wino_filter_transform_pc): that kernel lays out
 // tiles of 64 or 128 columns only.  conv_precut_tile answers 192 for widths in (128, 192] (the tile of the tail conv's input
 // gradient, produced by conv_precut) -- a stride-1 Winograd layer of such a width keeps its fp32 U and the kernels that read it,
 // and with them fp32 planes: planning and launch agree instead of failing at the first operand refresh (latent: no network of
 // the reference has a 3x3 / 4x4 stride-1 conv between 129 and 192 channels; swn_op_conv can ask for one).
-static int wino_precut_tile(int xC, int Npad) {
+int wino_precut_tile(int xC, int Npad) {
   const int t = conv_precut_tile(xC, Npad);
   return (t == 64 || t == 128) ? t : 0;
 }
-static bool wino_fwd_takes_pairs(int xC, int Npad) { return wino_precut_tile(xC, Npad) != 0 && conv_fwd_takes_pairs(xC, Npad); }
+bool wino_fwd_takes_pairs(int xC, int Npad) { return wino_precut_tile(xC, Npad) != 0 && conv_fwd_takes_pairs(xC, Npad); }
 
+bool bias_on_main() { static const bool on = env_on(getenv("SWN_BIAS_MAIN")); return on; }
+}  // namespace
+
+// What every route builder of a layer needs (Net::conv / Net::convT fill it; it lives for the builder's call only, so the
+// closures copy what they keep).  convT: kind / Ci / actf / geo / x_is_input / dgrad_C are not used.
+struct Net::ConvLayer {
+  const std::string& name;
+  const Var &x, &y;
+  ConvKind kind;
+  int Ci, Co, Cip, Cop;     // logical and buffer channels of input and output
+  int wi, bi;               // arena entries of weight and bias (bi < 0: none)
+  int actf;
+  ConvGeom geo;
+  bool x_is_input;
+  int dgrad_C;
+};
+
+// ---- Conv2d ---------------------------------------------------------------------------
+// y.v receives act(conv(x)+bias).  In backward y.g is the gradient w.r.t. that output.
 void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kind, int Ci, int Co, bool bias,
                int actf, const std::vector<int32_t>* cimap, bool x_is_input, int dgrad_C) {
+  const WinoSwitches sw = wino_switches();
   const int KH = kind == CK_K1S1 ? 1 : ((kind == CK_K3S1_REFLECT || kind == CK_K3S1_ZERO) ? 3 : 4);
   const ConvGeom geo = conv_geom(kind, x.v.H, x.v.W);
   if (y.v.H != geo.Ho || y.v.W != geo.Wo) throw Error(1, "conv " + name + ": output view has the wrong size");
@@ -308,312 +376,271 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
   note_act(actf, y.v);
 
   auto op = std::make_unique<Op>();
-  Op* self = op.get();
   op->label = name;
   op->param_off = arena.params[wi].off;
   op->reads_net_input = x_is_input;
-  ParamArena* A = &arena;
-  const Gather gf = geo.fwd;
-  const TView xv = x.v, yv = y.v;
+  const ConvLayer L{name, x, y, kind, Ci, Co, Cip, Cop, wi, bi, actf, geo, x_is_input, dgrad_C};
   // PatchGAN's 1-channel head conv (discriminators.py:131): taps on the N axis (ops.h head_*): the input
   // is read once by a 1x1 conv with N = 16 instead of 16 times by an N = 1 implicit GEMM.
-  const bool head_on = !(getenv("SWN_HEAD_TAPN") && atoi(getenv("SWN_HEAD_TAPN")) == 0);
-  if (head_on && kind == CK_K4S1 && Co == 1 && Cip % 32 == 0 && actf == ACT_NONE && x.has_grad == y.has_grad) {
-    const size_t wt_off = reserve_dg(self, (size_t)Cip * 16), wt2_off = reserve_dg(self, (size_t)16 * Cip);
-    const size_t dwt_off = reserve_dg(self, (size_t)Cip * 16);
-    note_writer(y.vbase, false);
-    Var Z = alloc_var(xv.N, xv.H, xv.W, 16, false);          // Z forward, dZ backward (same scratch)
-    const TView zv = Z.v, ygv = y.g, xgv = x.g;
-    const bool has_grad = y.has_grad;
-    op->repack = [=](Net& n) {
-      const ParamDesc& wd = A->params[wi];
-      head_pack(n.ctx.s, wd.ws, A->w + wd.off, n.dg + wt_off, n.dg + wt2_off);
-    };
-    op->fwd = [=](Net& n) {
-      n.need(self);
-      ConvFwdArgs a;
-      a.x = xv; a.g.Ho = xv.H; a.g.Wo = xv.W;               // 1x1, stride 1
-      a.w = n.dg + wt_off; a.Npad = 16; a.Cout = 16; a.y = zv;
-      conv_fwd(n.ctx.s, a);
-      head_gather(n.ctx.s, zv, bi >= 0 ? A->w + A->params[bi].off : nullptr, yv);
-    };
-    if (has_grad) op->grad_targets.push_back(x);
-    op->bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
-      if (!has_grad) return;
-      const ParamDesc& wd = A->params[wi];
-      head_scatter(n.ctx.s, ygv, zv);
-      if (wgrad) {
-        Stream& sw = n.wgrad_stream();
-        ConvWgradArgs wa;
-        wa.x = xv; wa.g.Ho = xv.H; wa.g.Wo = xv.W; wa.dy = zv;
-        wa.dw = n.dg + dwt_off; wa.Npad = 16; wa.Cout = 16;
-        conv_wgrad(sw, wa);
-        head_unpack_grad(sw, wd.ws, n.dg + dwt_off, A->g + wd.off);
-        if (bi >= 0) n.bias_grad_of(sw, ygv, A->g + A->params[bi].off);
-      }
-      if (me.reads_net_input && !igrad) return;
-      ConvFwdArgs d;
-      d.x = zv; d.g.Ho = xv.H; d.g.Wo = xv.W;
-      d.w = n.dg + wt2_off; d.Npad = Cip; d.Cout = Cip; d.y = xgv; d.accumulate = me.acc.empty() ? 0 : me.acc[0];
-      conv_fwd(n.ctx.s, d);
-    };
-    ops.push_back(std::move(op));
-    return;
-  }
+  if (env_on(getenv("SWN_HEAD_TAPN")) && kind == CK_K4S1 && Co == 1 && Cip % 32 == 0 && actf == ACT_NONE && x.has_grad == y.has_grad)
+    conv_head_tapn(L, *op);
   // k4 s2 convs with enough channels: strided Winograd F(4x4,2x2) (four polyphase 2x2 convolutions in one batched GEMM)
   // (never the layers that read a network input: their buffers carry layout pad channels -- 19 -> 32, 22 -> 32 -- that would
   // be transformed for nothing, and the channel threshold of the test routing must not reach them through the padding)
-  if (kind == CK_K4S2 && s2_wino && !x_is_input && s2_wino_wanted(Cip, Cop, y.v.H, y.v.W) && Co % 4 == 0) {
-    const int sP = 25, sTh = ceil_div(y.v.H, 4), sTw = ceil_div(y.v.W, 4), CV = 4 * Cip;
-    const size_t sT = (size_t)x.v.N * sTh * sTw;
-    const bool want_dx = x.has_grad && y.has_grad;
-    const size_t uf_off = reserve_dg(self, (size_t)sP * CV * Cop);                      // U  [25][4 Cip][Cop]
-    const size_t ut_off = want_dx ? reserve_dg(self, (size_t)sP * Cop * CV) : 0;        // U^T[25][Cop][4 Cip]
-    float* keepV = (keep_wino_inputs && y.has_grad) ? static_cast<float*>(ctx.alloc(sP * sT * CV * sizeof(float))) : nullptr;
-    wsV_need = std::max(wsV_need, sP * sT * (size_t)std::max(CV, Cop));
-    wsM_need = std::max(wsM_need, sP * sT * (size_t)std::max(CV, Cop));
-    wsU_need = std::max(wsU_need, (size_t)sP * CV * Cop);
-    const int pcf = conv_precut_tile(CV, Cop), pct = want_dx ? conv_precut_tile(Cop, CV) : 0;
-    const size_t pcf_bs = pcf ? conv_precut_elems(CV, Cop, pcf) : 0, pct_bs = pct ? conv_precut_elems(Cop, CV, pct) : 0;
-    const size_t pcf_off = pcf ? reserve_dgp(pcf_bs * sP) : 0, pct_off = pct ? reserve_dgp(pct_bs * sP) : 0;
-    const size_t slV = reserve_slot(), slD = reserve_slot();      // amax of V (forward planes) and of dM (transformed dY)
-    note_writer(y.vbase, false);
-    // pair-form planes (ops.h wino_input_transform) where every GEMM that reads them takes the kernels that can, and -- decided
-    // per pass -- the transform's input has a complete amax slot to bound the planes with
-    const bool pairV_ok = conv_fwd_takes_pairs(CV, Cop) && (!y.has_grad || conv_wgrad_takes_pairs(sT, CV, Cop));
-    const bool pairD_ok = conv_wgrad_takes_pairs(sT, CV, Cop) && (!(x.has_grad && y.has_grad) || conv_fwd_takes_pairs(Cop, CV));
-    const size_t kV = reserve_k(), kD = reserve_k();
-    const float* xbase = x.vbase; const float* ygbase = y.gbase;
-    // dM = A dY A^T serves the weight gradient (side stream) and the input gradient (main stream): one buffer per layer
-    float* keepdM = (y.has_grad && want_dx && share_dy()) ? static_cast<float*>(ctx.alloc(sP * sT * Cop * sizeof(float))) : nullptr;
-    op->repack = [=](Net& n) {
-      const ParamDesc& wd = A->params[wi];
-      const float* wmax = nullptr;       // U^T holds U's values: one amax pass serves both operands (ops.h conv_precut amax_io)
-      wino_s2_filter_transform(n.ctx.s, wd.ws, 0, A->w + wd.off, n.dg + uf_off);
-      if (pcf) conv_precut(n.ctx.s, n.dg + uf_off, CV, Cop, pcf, sP, (size_t)CV * Cop, n.dgp + pcf_off, &wmax);
-      if (want_dx) {
-        wino_s2_filter_transform(n.ctx.s, wd.ws, 1, A->w + wd.off, n.dg + ut_off);
-        if (pct) conv_precut(n.ctx.s, n.dg + ut_off, Cop, CV, pct, sP, (size_t)Cop * CV, n.dgp + pct_off, &wmax);
-      }
-    };
-    op->fwd = [=](Net& n) {
-      n.need(self);
-      float* V = keepV ? keepV : n.wsV;
-      const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
-      wino_s2_input_transform(n.ctx.s, xv, sTh, sTw, V, n.amax + slV, xin, n.kscale + kV);
-      ConvFwdArgs g;
-      g.x = plane_mat(V, sT, CV); g.g.Ho = 1; g.g.Wo = (int)sT;
-      g.w = n.dg + uf_off; g.Npad = Cop; g.Cout = Co;
-      g.y = plane_mat(n.wsM, sT, Cop);
-      g.batch = sP; g.x_bs = sT * CV; g.w_bs = (size_t)CV * Cop; g.y_bs = sT * Cop;
-      if (xin) g.x_pair_k = n.kscale + kV; else g.x_amax = n.amax + slV;
-      if (pcf) { g.wpc = n.dgp + pcf_off; g.wpc_bn = pcf; g.wpc_bs = pcf_bs; }
-      conv_fwd(n.ctx.s, g);
-      wino_output_transform(n.ctx.s, 4, 2, n.wsM, Cop, sTh, sTw, bi >= 0 ? A->w + A->params[bi].off : nullptr, actf, yv, Co, 0);
-    };
-    Var scratch;
-    if (y.has_grad && actf != ACT_NONE) scratch = alloc_var(yv.N, yv.H, yv.W, Cop, false);
-    if (want_dx) op->grad_targets.push_back(x);
-    const TView ygv = y.g, xgv = x.g, scr = scratch.v;
-    const bool has_ygrad = y.has_grad;
-    op->bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
-      if (!has_ygrad) return;
-      TView dY = ygv;
-      // (a fused activation's dR has no amax slot in this branch: its planes stay fp32 and the GEMM takes their amax)
-      if (actf != ACT_NONE) { act_bwd(n.ctx.s, ygv, yv, scr, actf, 0); dY = scr; }
-      const ParamDesc& wd = A->params[wi];
-      const bool dx_now = want_dx && !(me.reads_net_input && !igrad);
-      const bool shared = keepdM && wgrad && dx_now;       // one transform of dY on the main stream, read by both gradients
-      const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
-      const float* din = (pairD_ok && actf == ACT_NONE) ? n.slot_if_complete(ygbase) : nullptr;
-      if (shared) wino_dy_transform(n.ctx.s, 4, 2, dY, sTh, sTw, keepdM, n.amax + slD, din, n.kscale + kD);
-      if (wgrad) {
-        Stream& sw = n.wgrad_stream();
-        float* V = keepV ? keepV : n.wsV;
-        float* dM = shared ? keepdM : n.wgrad_planes(sw);
-        if (!keepV) wino_s2_input_transform(sw, xv, sTh, sTw, V, n.amax + slV, xin, n.kscale + kV);
-        if (!shared) wino_dy_transform(sw, 4, 2, dY, sTh, sTw, dM, n.amax + slD, din, n.kscale + kD);
-        ConvWgradArgs g;
-        g.x = plane_mat(V, sT, CV); g.g.Ho = 1; g.g.Wo = (int)sT;
-        g.dy = plane_mat(dM, sT, Cop);
-        g.dw = n.wsU; g.Npad = Cop; g.Cout = Co;
-        g.batch = sP; g.x_bs = sT * CV; g.dy_bs = sT * Cop; g.dw_bs = (size_t)CV * Cop;
-        if (xin) g.x_pair_k = n.kscale + kV; else g.x_amax = n.amax + slV;
-        if (din) g.dy_pair_k = n.kscale + kD; else g.dy_amax = n.amax + slD;
-        conv_wgrad(sw, g);
-        wino_s2_filter_grad(sw, wd.ws, n.wsU, A->g + wd.off);
-        if (bi >= 0) n.bias_grad_of(sw, dY, A->g + A->params[bi].off);
-      }
-      if (!dx_now) return;
-      float* dMx = shared ? keepdM : n.wsV;
-      if (!shared) wino_dy_transform(n.ctx.s, 4, 2, dY, sTh, sTw, dMx, n.amax + slD, din, n.kscale + kD);
-      ConvFwdArgs g;
-      g.x = plane_mat(dMx, sT, Cop); g.g.Ho = 1; g.g.Wo = (int)sT;
-      g.w = n.dg + ut_off; g.Npad = CV; g.Cout = CV;
-      g.y = plane_mat(n.wsM, sT, CV);
-      g.batch = sP; g.x_bs = sT * Cop; g.w_bs = (size_t)Cop * CV; g.y_bs = sT * CV;
-      if (din) g.x_pair_k = n.kscale + kD; else g.x_amax = n.amax + slD;
-      if (pct) { g.wpc = n.dgp + pct_off; g.wpc_bn = pct; g.wpc_bs = pct_bs; }
-      conv_fwd(n.ctx.s, g);
-      wino_s2_input_adjoint(n.ctx.s, n.wsM, Cip, sTh, sTw, xgv, nullptr, me.acc.empty() ? 0 : me.acc[0]);
-    };
-    ops.push_back(std::move(op));
-    return;
-  }
+  else if (kind == CK_K4S2 && s2_wino && !x_is_input && s2_wino_wanted(sw, Cip, Cop, y.v.H, y.v.W) && Co % 4 == 0)
+    conv_wino_s2(L, *op);
   // The tail conv in Winograd form (ops.h tailw_*): the four folded sub-pixel phases share one F(4x4,3x3) input transform of the
   // un-upsampled map and one batched GEMM with N = 4 Npad; forward and weight gradient (the input gradient stays the folded
   // 5x5 stride-2 conv on the ring kernel: its Winograd form would be bound by the adjoint transform of a 0.9 GB operand)
-  if (kind == CK_TAIL_UP) {
-    const int twminc_env = getenv("SWN_WINO_MINC") ? atoi(getenv("SWN_WINO_MINC")) : 0;
-    const bool tw_on = !(getenv("SWN_WINOGRAD") && atoi(getenv("SWN_WINOGRAD")) == 0);
-    if (tw_on && Cip % 32 == 0 && Cip >= (twminc_env > 0 ? twminc_env : 64) && x.v.H >= 4 && x.v.W >= 4 && Cop <= 32) {
-      const ParamDesc wd0 = arena.params[wi];
-      const int tP = 36, tTh = ceil_div(x.v.H, 4), tTw = ceil_div(x.v.W, 4), N4 = 4 * Cop;
-      const size_t tT = (size_t)x.v.N * tTh * tTw;
-      const size_t fe = tail_fold_offset(wd0.ws, 4);
-      const size_t fold_off = reserve_dg(self, fe), dfold_off = reserve_dg(self, fe);
-      const size_t tu_off = reserve_dg(self, (size_t)tP * Cip * N4);
-      float* keepV = (keep_wino_inputs && y.has_grad) ? static_cast<float*>(ctx.alloc(tP * tT * Cip * sizeof(float))) : nullptr;
-      wsV_need = std::max(wsV_need, tP * tT * (size_t)std::max(Cip, N4));
-      wsM_need = std::max(wsM_need, tP * tT * (size_t)std::max(Cip, N4));
-      wsU_need = std::max(wsU_need, (size_t)tP * Cip * N4);
-      const int pcu = conv_precut_tile(Cip, N4);
-      const size_t pcu_bs = pcu ? conv_precut_elems(Cip, N4, pcu) : 0, pcu_off = pcu ? reserve_dgp(pcu_bs * tP) : 0;
-      const size_t slV = reserve_slot(), slD = reserve_slot();
-      note_writer(y.vbase, false);
-      const bool pairV_ok = conv_fwd_takes_pairs(Cip, N4) && (!y.has_grad || conv_wgrad_takes_pairs(tT, Cip, N4));
-      const bool pairD_ok = conv_wgrad_takes_pairs(tT, Cip, N4);
-      const size_t kV = reserve_k(), kD = reserve_k();
-      const float* xbase = x.vbase;
-      // input gradient: the folded 5x5 stride-2 conv over dR (32-channel buffer, see CopD below)
-      const bool want_dx = x.has_grad && y.has_grad;
-      const int CopD = (actf != ACT_NONE && want_dx && conv_precut_tile(32, Cip) == 192) ? 32 : Cop;
-      const size_t dg_off = want_dx ? reserve_dg(self, dgrad_elems(wd0.ws, 3, CopD, Cip)) : 0;
-      const int pc_d = want_dx ? conv_precut_tile(CopD, Cip) : 0;
-      const size_t pcd_bs = pc_d ? conv_precut_elems(25 * CopD, Cip, pc_d) : 0, pcd_off = pc_d ? reserve_dgp(pcd_bs) : 0;
-      op->repack = [=](Net& n) {
-        const ParamDesc& wd = A->params[wi];
-        tail_fold_weights(n.ctx.s, wd.ws, A->w + wd.off, n.dg + fold_off);
-        tailw_filter_transform(n.ctx.s, wd.ws, n.dg + fold_off, n.dg + tu_off);
-        if (pcu) conv_precut(n.ctx.s, n.dg + tu_off, Cip, N4, pcu, tP, (size_t)Cip * N4, n.dgp + pcu_off);
-        if (want_dx) {
-          repack_dgrad(n.ctx.s, wd.ws, 3, CopD, Cip, A->w + wd.off, n.dg + dg_off);
-          if (pc_d) conv_precut(n.ctx.s, n.dg + dg_off, 25 * CopD, Cip, pc_d, 1, 0, n.dgp + pcd_off);
-        }
-      };
-      op->fwd = [=](Net& n) {
-        n.need(self);
-        float* V = keepV ? keepV : n.wsV;
-        const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
-        wino_input_transform(n.ctx.s, 4, 3, xv, 1, PAD_ZERO, tTh, tTw, V, n.amax + slV, xin, n.kscale + kV);
-        ConvFwdArgs g;
-        g.x = plane_mat(V, tT, Cip); g.g.Ho = 1; g.g.Wo = (int)tT;
-        g.w = n.dg + tu_off; g.Npad = N4; g.Cout = N4;
-        g.y = plane_mat(n.wsM, tT, N4);
-        g.batch = tP; g.x_bs = tT * Cip; g.w_bs = (size_t)Cip * N4; g.y_bs = tT * N4;
-        if (xin) g.x_pair_k = n.kscale + kV; else g.x_amax = n.amax + slV;
-        if (pcu) { g.wpc = n.dgp + pcu_off; g.wpc_bn = pcu; g.wpc_bs = pcu_bs; }
-        conv_fwd(n.ctx.s, g);
-        tailw_output_transform(n.ctx.s, n.wsM, tTh, tTw, Cop, bi >= 0 ? A->w + A->params[bi].off : nullptr, actf, yv, Co);
-      };
-      Var scratch;
-      if (y.has_grad && actf != ACT_NONE) scratch = alloc_var(yv.N, yv.H, yv.W, CopD, false);
-      if (want_dx) op->grad_targets.push_back(x);
-      const TView ygv = y.g, xgv = x.g, scr = CopD != Cop ? scratch.v.slice(0, Cop) : scratch.v, scr_full = scratch.v;
-      const bool has_ygrad = y.has_grad;
-      const size_t scrSlot = (y.has_grad && actf != ACT_NONE) ? note_writer(scratch.v.p, true) : 0;
-      op->bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
-        if (!has_ygrad) return;
-        TView dY = ygv;
-        const float* dy_slot = nullptr;
-        if (actf != ACT_NONE) { act_bwd(n.ctx.s, ygv, yv, scr, actf, 0, n.amax + scrSlot); dY = scr; dy_slot = n.amax + scrSlot; }
-        const ParamDesc& wd = A->params[wi];
-        if (wgrad) {
-          Stream& sw = n.wgrad_stream();
-          float* V = keepV ? keepV : n.wsV;
-          float* dM = n.wgrad_planes(sw);
-          const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
-          const float* din = pairD_ok ? dy_slot : nullptr;
-          if (!keepV) wino_input_transform(sw, 4, 3, xv, 1, PAD_ZERO, tTh, tTw, V, n.amax + slV, xin, n.kscale + kV);
-          tailw_dy_transform(sw, dY, tTh, tTw, Cop, dM, n.amax + slD, din, n.kscale + kD);
-          ConvWgradArgs g;
-          g.x = plane_mat(V, tT, Cip); g.g.Ho = 1; g.g.Wo = (int)tT;
-          g.dy = plane_mat(dM, tT, N4);
-          g.dw = n.wsU; g.Npad = N4; g.Cout = N4;
-          g.batch = tP; g.x_bs = tT * Cip; g.dy_bs = tT * N4; g.dw_bs = (size_t)Cip * N4;
-          if (xin) g.x_pair_k = n.kscale + kV; else g.x_amax = n.amax + slV;
-          if (din) g.dy_pair_k = n.kscale + kD; else g.dy_amax = n.amax + slD;
-          conv_wgrad(sw, g);
-          tailw_filter_grad(sw, wd.ws, n.wsU, n.dg + dfold_off);
-          tail_unfold_wgrad(sw, wd.ws, n.dg + dfold_off, A->g + wd.off);
-          if (bi >= 0) n.bias_grad_of(sw, dY, A->g + A->params[bi].off);
-        }
-        if (!want_dx || (me.reads_net_input && !igrad)) return;
-        ConvFwdArgs d;
-        d.x = CopD != Cop ? scr_full : dY;
-        d.g.KH = d.g.KW = 5; d.g.stride = 2; d.g.pad_t = d.g.pad_l = 1; d.g.Ho = xv.H; d.g.Wo = xv.W;
-        d.w = n.dg + dg_off; d.Npad = Cip; d.Cout = Cip; d.y = xgv; d.accumulate = me.acc.empty() ? 0 : me.acc[0];
-        d.x_amax = dy_slot;
-        if (pc_d) { d.wpc = n.dgp + pcd_off; d.wpc_bn = pc_d; d.wpc_bs = pcd_bs; }
-        conv_fwd(n.ctx.s, d);
-      };
-      ops.push_back(std::move(op));
-      return;
+  else if (kind == CK_TAIL_UP && sw.on && Cip % 32 == 0 && Cip >= (sw.minc > 0 ? sw.minc : 64) && x.v.H >= 4 && x.v.W >= 4 && Cop <= 32)
+    conv_tail_wino(L, *op);
+  else if (const int wm = wino_s1_m(sw, kind, Cip, Co, x.v.H, x.v.W))
+    conv_wino_s1(L, wm, *op);
+  else
+    conv_direct(L, *op);
+  ops.push_back(std::move(op));
+}
+
+void Net::conv_head_tapn(const ConvLayer& L, Op& op) {
+  const Var &x = L.x, &y = L.y;
+  const int Cip = L.Cip, wi = L.wi, bi = L.bi;
+  ParamArena* A = &arena; Op* self = &op;
+  const TView xv = x.v, yv = y.v;
+  const size_t wt_off = reserve_dg(self, (size_t)Cip * 16), wt2_off = reserve_dg(self, (size_t)16 * Cip);
+  const size_t dwt_off = reserve_dg(self, (size_t)Cip * 16);
+  note_writer(y.vbase, false);
+  Var Z = alloc_var(xv.N, xv.H, xv.W, 16, false);          // Z forward, dZ backward (same scratch)
+  const TView zv = Z.v, ygv = y.g, xgv = x.g;
+  const bool has_grad = y.has_grad;
+  op.repack = [=](Net& n) {
+    const ParamDesc& wd = A->params[wi];
+    head_pack(n.ctx.s, wd.ws, A->w + wd.off, n.dg + wt_off, n.dg + wt2_off);
+  };
+  op.fwd = [=](Net& n) {
+    n.need(self);
+    ConvFwdArgs a;
+    a.x = xv; a.g.Ho = xv.H; a.g.Wo = xv.W;               // 1x1, stride 1
+    a.w = n.dg + wt_off; a.Npad = 16; a.Cout = 16; a.y = zv;
+    conv_fwd(n.ctx.s, a);
+    head_gather(n.ctx.s, zv, bi >= 0 ? A->w + A->params[bi].off : nullptr, yv);
+  };
+  if (has_grad) op.grad_targets.push_back(x);
+  op.bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
+    if (!has_grad) return;
+    const ParamDesc& wd = A->params[wi];
+    head_scatter(n.ctx.s, ygv, zv);
+    if (wgrad) {
+      Stream& sw = n.wgrad_stream();
+      ConvWgradArgs wa;
+      wa.x = xv; wa.g.Ho = xv.H; wa.g.Wo = xv.W; wa.dy = zv;
+      wa.dw = n.dg + dwt_off; wa.Npad = 16; wa.Cout = 16;
+      conv_wgrad(sw, wa);
+      head_unpack_grad(sw, wd.ws, n.dg + dwt_off, A->g + wd.off);
+      if (bi >= 0) n.bias_grad_of(sw, ygv, A->g + A->params[bi].off);
     }
-  }
-  // tail conv: run as 4 folded sub-pixel phases on the un-upsampled input (25 instead of 64
-  // taps per 2x2 outputs; see ops.h tail_fold_weights).  The folded weights and the folded
-  // weight-gradient scratch live next to the dgrad operands and follow arena.version.
-  const bool folded = kind == CK_TAIL_UP;
-  size_t fold_off = 0, dfold_off = 0;
-  if (folded) {
-    const size_t fe = tail_fold_offset(arena.params[wi].ws, 4);
-    fold_off = reserve_dg(self, fe);
-    dfold_off = reserve_dg(self, fe);
-  }
-  // Stride-1 convs with MFMA-friendly channel counts run as Winograd F(m x m, r x r): transform,
-  // (m+r-1)^2 batched GEMMs, inverse transform (wino.hip).  3x3: F(4x4,3x3) when H and W are
-  // multiples of 4 (4x fewer multiplies), else F(2x2,3x3) (2.25x); PatchGAN's k4 s1: F(3x3,4x4) (4x).
-  const bool wino_on = !(getenv("SWN_WINOGRAD") && atoi(getenv("SWN_WINOGRAD")) == 0);
-  // ... when the channel counts are large enough for the GEMMs (K = Cin each) to run at MFMA speed
-  // and to amortise the HBM-bound transforms: measured on VGG16 (texture C3), the 6-point forms win
-  // from 64 channels up, F(2x2,3x3) (4x instead of 2.25x transform data per input) only from 256
-  const int wino_minc_env = getenv("SWN_WINO_MINC") ? atoi(getenv("SWN_WINO_MINC")) : 0;
-  const int wino_force_m = getenv("SWN_WINO_M") ? atoi(getenv("SWN_WINO_M")) : 0;
-  const bool wino_k4 = true;
-  const bool is_k3 = kind == CK_K3S1_REFLECT || kind == CK_K3S1_ZERO;
-  const bool is_k4 = kind == CK_K4S1 && wino_k4;
-  const int wr = is_k4 ? 4 : 3;
-  const int wm = is_k4 ? 3 : ((wino_force_m != 2 && x.v.H % 4 == 0 && x.v.W % 4 == 0) ? 4 : 2);
-  const int wino_minc = wino_minc_env > 0 ? wino_minc_env : (wm == 2 ? 256 : 64);
-  const bool wino = wino_on && Cip % 32 == 0 && Co % 32 == 0 && Cip >= wino_minc && Co >= wino_minc && x.v.H >= 4 &&
-                    x.v.W >= 4 && ((is_k3 && x.v.H % 2 == 0 && x.v.W % 2 == 0) || is_k4);
+    if (me.reads_net_input && !igrad) return;
+    ConvFwdArgs d;
+    d.x = zv; d.g.Ho = xv.H; d.g.Wo = xv.W;
+    d.w = n.dg + wt2_off; d.Npad = Cip; d.Cout = Cip; d.y = xgv; d.accumulate = me.acc.empty() ? 0 : me.acc[0];
+    conv_fwd(n.ctx.s, d);
+  };
+}
+
+void Net::conv_wino_s2(const ConvLayer& L, Op& op) {
+  const Var &x = L.x, &y = L.y;
+  const int Co = L.Co, Cip = L.Cip, Cop = L.Cop, wi = L.wi, bi = L.bi, actf = L.actf;
+  ParamArena* A = &arena; Op* self = &op;
+  const TView xv = x.v, yv = y.v;
+  const int sP = 25, sTh = ceil_div(y.v.H, 4), sTw = ceil_div(y.v.W, 4), CV = 4 * Cip;
+  const size_t sT = (size_t)x.v.N * sTh * sTw;
+  const bool want_dx = x.has_grad && y.has_grad;
+  const size_t uf_off = reserve_dg(self, (size_t)sP * CV * Cop);                      // U  [25][4 Cip][Cop]
+  const size_t ut_off = want_dx ? reserve_dg(self, (size_t)sP * Cop * CV) : 0;        // U^T[25][Cop][4 Cip]
+  float* keepV = (keep_wino_inputs && y.has_grad) ? static_cast<float*>(ctx.alloc(sP * sT * CV * sizeof(float))) : nullptr;
+  wsV_need = std::max(wsV_need, sP * sT * (size_t)std::max(CV, Cop));
+  wsM_need = std::max(wsM_need, sP * sT * (size_t)std::max(CV, Cop));
+  wsU_need = std::max(wsU_need, (size_t)sP * CV * Cop);
+  const int pcf = conv_precut_tile(CV, Cop), pct = want_dx ? conv_precut_tile(Cop, CV) : 0;
+  const size_t pcf_bs = pcf ? conv_precut_elems(CV, Cop, pcf) : 0, pct_bs = pct ? conv_precut_elems(Cop, CV, pct) : 0;
+  const size_t pcf_off = pcf ? reserve_dgp(pcf_bs * sP) : 0, pct_off = pct ? reserve_dgp(pct_bs * sP) : 0;
+  const size_t slV = reserve_slot(), slD = reserve_slot();      // amax of V (forward planes) and of dM (transformed dY)
+  note_writer(y.vbase, false);
+  // pair-form planes (ops.h wino_input_transform) where every GEMM that reads them takes the kernels that can, and -- decided
+  // per pass -- the transform's input has a complete amax slot to bound the planes with
+  const bool pairV_ok = conv_fwd_takes_pairs(CV, Cop) && (!y.has_grad || conv_wgrad_takes_pairs(sT, CV, Cop));
+  const bool pairD_ok = conv_wgrad_takes_pairs(sT, CV, Cop) && (!(x.has_grad && y.has_grad) || conv_fwd_takes_pairs(Cop, CV));
+  const size_t kV = reserve_k(), kD = reserve_k();
+  const float* xbase = x.vbase; const float* ygbase = y.gbase;
+  // dM = A dY A^T serves the weight gradient (side stream) and the input gradient (main stream): one buffer per layer
+  float* keepdM = (y.has_grad && want_dx && share_dy()) ? static_cast<float*>(ctx.alloc(sP * sT * Cop * sizeof(float))) : nullptr;
+  op.repack = [=](Net& n) {
+    const ParamDesc& wd = A->params[wi];
+    const float* wmax = nullptr;       // U^T holds U's values: one amax pass serves both operands (ops.h conv_precut amax_io)
+    wino_s2_filter_transform(n.ctx.s, wd.ws, 0, A->w + wd.off, n.dg + uf_off);
+    if (pcf) conv_precut(n.ctx.s, n.dg + uf_off, CV, Cop, pcf, sP, (size_t)CV * Cop, n.dgp + pcf_off, &wmax);
+    if (want_dx) {
+      wino_s2_filter_transform(n.ctx.s, wd.ws, 1, A->w + wd.off, n.dg + ut_off);
+      if (pct) conv_precut(n.ctx.s, n.dg + ut_off, Cop, CV, pct, sP, (size_t)Cop * CV, n.dgp + pct_off, &wmax);
+    }
+  };
+  op.fwd = [=](Net& n) {
+    n.need(self);
+    float* V = keepV ? keepV : n.wsV;
+    const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
+    wino_s2_input_transform(n.ctx.s, xv, sTh, sTw, V, n.amax + slV, xin, n.kscale + kV);
+    conv_fwd(n.ctx.s, plane_gemm(V, n.wsM, sT, CV, Cop, Co, sP, plane_scale(xin != nullptr, n.kscale + kV, n.amax + slV),
+                                 {n.dg + uf_off, n.dgp + pcf_off, pcf, pcf_bs}));
+    wino_output_transform(n.ctx.s, 4, 2, n.wsM, Cop, sTh, sTw, bi >= 0 ? A->w + A->params[bi].off : nullptr, actf, yv, Co, 0);
+  };
+  Var scratch;
+  if (y.has_grad && actf != ACT_NONE) scratch = alloc_var(yv.N, yv.H, yv.W, Cop, false);
+  if (want_dx) op.grad_targets.push_back(x);
+  const TView ygv = y.g, xgv = x.g, scr = scratch.v;
+  const bool has_ygrad = y.has_grad;
+  op.bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
+    if (!has_ygrad) return;
+    TView dY = ygv;
+    // (a fused activation's dR has no amax slot in this branch: its planes stay fp32 and the GEMM takes their amax)
+    if (actf != ACT_NONE) { act_bwd(n.ctx.s, ygv, yv, scr, actf, 0); dY = scr; }
+    const ParamDesc& wd = A->params[wi];
+    const bool dx_now = want_dx && !(me.reads_net_input && !igrad);
+    const bool shared = keepdM && wgrad && dx_now;       // one transform of dY on the main stream, read by both gradients
+    const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
+    const float* din = (pairD_ok && actf == ACT_NONE) ? n.slot_if_complete(ygbase) : nullptr;
+    const PlaneScale dMs = plane_scale(din != nullptr, n.kscale + kD, n.amax + slD);
+    if (shared) wino_dy_transform(n.ctx.s, 4, 2, dY, sTh, sTw, keepdM, n.amax + slD, din, n.kscale + kD);
+    if (wgrad) {
+      Stream& sw = n.wgrad_stream();
+      float* V = keepV ? keepV : n.wsV;
+      float* dM = shared ? keepdM : n.wgrad_planes(sw);
+      if (!keepV) wino_s2_input_transform(sw, xv, sTh, sTw, V, n.amax + slV, xin, n.kscale + kV);
+      if (!shared) wino_dy_transform(sw, 4, 2, dY, sTh, sTw, dM, n.amax + slD, din, n.kscale + kD);
+      conv_wgrad(sw, plane_wgrad(V, dM, n.wsU, sT, CV, Cop, Co, sP, plane_scale(xin != nullptr, n.kscale + kV, n.amax + slV), dMs));
+      wino_s2_filter_grad(sw, wd.ws, n.wsU, A->g + wd.off);
+      if (bi >= 0) n.bias_grad_of(sw, dY, A->g + A->params[bi].off);
+    }
+    if (!dx_now) return;
+    float* dMx = shared ? keepdM : n.wsV;
+    if (!shared) wino_dy_transform(n.ctx.s, 4, 2, dY, sTh, sTw, dMx, n.amax + slD, din, n.kscale + kD);
+    conv_fwd(n.ctx.s, plane_gemm(dMx, n.wsM, sT, Cop, CV, CV, sP, dMs, {n.dg + ut_off, n.dgp + pct_off, pct, pct_bs}));
+    wino_s2_input_adjoint(n.ctx.s, n.wsM, Cip, sTh, sTw, xgv, nullptr, me.acc.empty() ? 0 : me.acc[0]);
+  };
+}
+
+void Net::conv_tail_wino(const ConvLayer& L, Op& op) {
+  const Var &x = L.x, &y = L.y;
+  const int Co = L.Co, Cip = L.Cip, Cop = L.Cop, wi = L.wi, bi = L.bi, actf = L.actf;
+  ParamArena* A = &arena; Op* self = &op;
+  const TView xv = x.v, yv = y.v;
+  const ParamDesc wd0 = arena.params[wi];
+  const int tP = 36, tTh = ceil_div(x.v.H, 4), tTw = ceil_div(x.v.W, 4), N4 = 4 * Cop;
+  const size_t tT = (size_t)x.v.N * tTh * tTw;
+  const size_t fe = tail_fold_offset(wd0.ws, 4);
+  const size_t fold_off = reserve_dg(self, fe), dfold_off = reserve_dg(self, fe);
+  const size_t tu_off = reserve_dg(self, (size_t)tP * Cip * N4);
+  float* keepV = (keep_wino_inputs && y.has_grad) ? static_cast<float*>(ctx.alloc(tP * tT * Cip * sizeof(float))) : nullptr;
+  wsV_need = std::max(wsV_need, tP * tT * (size_t)std::max(Cip, N4));
+  wsM_need = std::max(wsM_need, tP * tT * (size_t)std::max(Cip, N4));
+  wsU_need = std::max(wsU_need, (size_t)tP * Cip * N4);
+  const int pcu = conv_precut_tile(Cip, N4);
+  const size_t pcu_bs = pcu ? conv_precut_elems(Cip, N4, pcu) : 0, pcu_off = pcu ? reserve_dgp(pcu_bs * tP) : 0;
+  const size_t slV = reserve_slot(), slD = reserve_slot();
+  note_writer(y.vbase, false);
+  const bool pairV_ok = conv_fwd_takes_pairs(Cip, N4) && (!y.has_grad || conv_wgrad_takes_pairs(tT, Cip, N4));
+  const bool pairD_ok = conv_wgrad_takes_pairs(tT, Cip, N4);
+  const size_t kV = reserve_k(), kD = reserve_k();
+  const float* xbase = x.vbase;
+  // input gradient: the folded 5x5 stride-2 conv over dR (32-channel buffer, see CopD in conv_direct)
+  const bool want_dx = x.has_grad && y.has_grad;
+  const int CopD = (actf != ACT_NONE && want_dx && conv_precut_tile(32, Cip) == 192) ? 32 : Cop;
+  const size_t dg_off = want_dx ? reserve_dg(self, dgrad_elems(wd0.ws, 3, CopD, Cip)) : 0;
+  const int pc_d = want_dx ? conv_precut_tile(CopD, Cip) : 0;
+  const size_t pcd_bs = pc_d ? conv_precut_elems(25 * CopD, Cip, pc_d) : 0, pcd_off = pc_d ? reserve_dgp(pcd_bs) : 0;
+  op.repack = [=](Net& n) {
+    const ParamDesc& wd = A->params[wi];
+    tail_fold_weights(n.ctx.s, wd.ws, A->w + wd.off, n.dg + fold_off);
+    tailw_filter_transform(n.ctx.s, wd.ws, n.dg + fold_off, n.dg + tu_off);
+    if (pcu) conv_precut(n.ctx.s, n.dg + tu_off, Cip, N4, pcu, tP, (size_t)Cip * N4, n.dgp + pcu_off);
+    if (want_dx) {
+      repack_dgrad(n.ctx.s, wd.ws, 3, CopD, Cip, A->w + wd.off, n.dg + dg_off);
+      if (pc_d) conv_precut(n.ctx.s, n.dg + dg_off, 25 * CopD, Cip, pc_d, 1, 0, n.dgp + pcd_off);
+    }
+  };
+  op.fwd = [=](Net& n) {
+    n.need(self);
+    float* V = keepV ? keepV : n.wsV;
+    const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
+    wino_input_transform(n.ctx.s, 4, 3, xv, 1, PAD_ZERO, tTh, tTw, V, n.amax + slV, xin, n.kscale + kV);
+    conv_fwd(n.ctx.s, plane_gemm(V, n.wsM, tT, Cip, N4, N4, tP, plane_scale(xin != nullptr, n.kscale + kV, n.amax + slV),
+                                 {n.dg + tu_off, n.dgp + pcu_off, pcu, pcu_bs}));
+    tailw_output_transform(n.ctx.s, n.wsM, tTh, tTw, Cop, bi >= 0 ? A->w + A->params[bi].off : nullptr, actf, yv, Co);
+  };
+  Var scratch;
+  if (y.has_grad && actf != ACT_NONE) scratch = alloc_var(yv.N, yv.H, yv.W, CopD, false);
+  if (want_dx) op.grad_targets.push_back(x);
+  const TView ygv = y.g, xgv = x.g, scr = CopD != Cop ? scratch.v.slice(0, Cop) : scratch.v, scr_full = scratch.v;
+  const bool has_ygrad = y.has_grad;
+  const size_t scrSlot = (y.has_grad && actf != ACT_NONE) ? note_writer(scratch.v.p, true) : 0;
+  op.bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
+    if (!has_ygrad) return;
+    TView dY = ygv;
+    const float* dy_slot = nullptr;
+    if (actf != ACT_NONE) { act_bwd(n.ctx.s, ygv, yv, scr, actf, 0, n.amax + scrSlot); dY = scr; dy_slot = n.amax + scrSlot; }
+    const ParamDesc& wd = A->params[wi];
+    if (wgrad) {
+      Stream& sw = n.wgrad_stream();
+      float* V = keepV ? keepV : n.wsV;
+      float* dM = n.wgrad_planes(sw);
+      const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
+      const float* din = pairD_ok ? dy_slot : nullptr;
+      if (!keepV) wino_input_transform(sw, 4, 3, xv, 1, PAD_ZERO, tTh, tTw, V, n.amax + slV, xin, n.kscale + kV);
+      tailw_dy_transform(sw, dY, tTh, tTw, Cop, dM, n.amax + slD, din, n.kscale + kD);
+      conv_wgrad(sw, plane_wgrad(V, dM, n.wsU, tT, Cip, N4, N4, tP, plane_scale(xin != nullptr, n.kscale + kV, n.amax + slV),
+                                 plane_scale(din != nullptr, n.kscale + kD, n.amax + slD)));
+      tailw_filter_grad(sw, wd.ws, n.wsU, n.dg + dfold_off);
+      tail_unfold_wgrad(sw, wd.ws, n.dg + dfold_off, A->g + wd.off);
+      if (bi >= 0) n.bias_grad_of(sw, dY, A->g + A->params[bi].off);
+    }
+    if (!want_dx || (me.reads_net_input && !igrad)) return;
+    ConvFwdArgs d;
+    d.x = CopD != Cop ? scr_full : dY;
+    d.g.KH = d.g.KW = 5; d.g.stride = 2; d.g.pad_t = d.g.pad_l = 1; d.g.Ho = xv.H; d.g.Wo = xv.W;
+    d.w = n.dg + dg_off; d.Npad = Cip; d.Cout = Cip; d.y = xgv; d.accumulate = me.acc.empty() ? 0 : me.acc[0];
+    d.x_amax = dy_slot;
+    if (pc_d) { d.wpc = n.dgp + pcd_off; d.wpc_bn = pc_d; d.wpc_bs = pcd_bs; }
+    conv_fwd(n.ctx.s, d);
+  };
+}
+
+// Stride-1 Winograd F(wm x wm, r x r), r from the kernel size (the predicate and its reasons: wino_s1_m)
+void Net::conv_wino_s1(const ConvLayer& L, int wm, Op& op) {
+  const Var &x = L.x, &y = L.y;
+  const ConvKind kind = L.kind;
+  const int Co = L.Co, Cip = L.Cip, Cop = L.Cop, wi = L.wi, bi = L.bi, actf = L.actf;
+  ParamArena* A = &arena; Op* self = &op;
+  const Gather gf = L.geo.fwd;
+  const TView xv = x.v, yv = y.v;
+  const int wr = kind == CK_K4S1 ? 4 : 3;
   const int wP = (wm + wr - 1) * (wm + wr - 1);
-  const int wN = x.v.N, wTh = ceil_div(y.v.H, wm), wTw = ceil_div(y.v.W, wm);
-  const size_t wT = (size_t)wN * wTh * wTw;
+  const int wTh = ceil_div(y.v.H, wm), wTw = ceil_div(y.v.W, wm);
+  const size_t wT = (size_t)x.v.N * wTh * wTw;
   // dgrad of the REFLECT-padded convs (the resblocks) = the adjoint of the forward Winograd pipeline, in the forward tiling:
   // dV = (A dY A^T) U^T, dx = adjoint input transform (ops.h wino_input_adjoint) -- 16 tiles per 16x16 map where the
-  // transposed-conv form below walks the 18x18 padded gradient grid in 25.  The zero-padded convs (VGG16, PatchGAN's k4 s1)
-  // keep the transposed stride-1 conv over dY (pad r-1-p): same tile count either way, and it is the better-conditioned form
-  // (its large-entry matrices B^T / A^T act on data, not on the GEMM's output).  SWN_WINO_ADJOINT=0/2: never / always adjoint.
-  const int wadj_env = 1;
-  const bool wadj = wadj_env == 2 || (wadj_env == 1 && kind == CK_K3S1_REFLECT);
+  // transposed-conv form walks the 18x18 padded gradient grid in 25.  The zero-padded convs (VGG16, PatchGAN's k4 s1)
+  // keep the transposed stride-1 conv over dY (pad r-1-p, tiles over the input grid): same tile count either way, and it is the
+  // better-conditioned form (its large-entry matrices B^T / A^T act on data, not on the GEMM's output).
+  const bool wadj = kind == CK_K3S1_REFLECT;
   const int wpad2 = kind == CK_K3S1_ZERO ? 1 : 2;
-  const int wTh2 = ceil_div(x.v.H + (kind == CK_K3S1_REFLECT ? 2 : 0), wm);
-  const int wTw2 = ceil_div(x.v.W + (kind == CK_K3S1_REFLECT ? 2 : 0), wm);
-  const size_t wT2 = wadj ? 0 : (size_t)wN * wTh2 * wTw2;
-  size_t uf_off = 0, ub_off = 0;
-  float* keepV = nullptr;         // V = B^T d B of the forward input, reused by the weight gradient
-  if (wino && keep_wino_inputs && y.has_grad) keepV = static_cast<float*>(ctx.alloc((size_t)wP * wT * Cip * sizeof(float)));
+  const int wTh2 = ceil_div(x.v.H, wm), wTw2 = ceil_div(x.v.W, wm);
+  const size_t wT2 = wadj ? 0 : (size_t)x.v.N * wTh2 * wTw2;
+  // V = B^T d B of the forward input, reused by the weight gradient
+  float* keepV = (keep_wino_inputs && y.has_grad) ? static_cast<float*>(ctx.alloc((size_t)wP * wT * Cip * sizeof(float))) : nullptr;
   // 6-point forms: the transformed filters go straight into the pre-cut operand layout of the ring kernel (no fp32 U)
-  const int pcw = (wino && wm != 2) ? wino_precut_tile(Cip, Cop) : 0;
+  const int pcw = wm != 2 ? wino_precut_tile(Cip, Cop) : 0;
   const size_t pcw_bs = pcw ? conv_precut_elems(Cip, Cop, pcw) : 0;
-  size_t pcw_off = 0, pcwt_off = 0;
-  int pcwt = 0;
-  size_t pcwt_bs = 0;
   // amax slots of the Winograd-domain operands: V (forward planes), dM (transformed dY), dX (the padded dY planes of the
   // transposed-conv form of the input gradient); the 6-point forms only (F(2,3) planes feed the fp32-operand kernels)
-  const bool wslots = wino && wm != 2;
+  const bool wslots = wm != 2;
   const size_t slV = wslots ? reserve_slot() : 0, slD = wslots ? reserve_slot() : 0, slX = wslots ? reserve_slot() : 0;
   // pair-form planes (ops.h wino_input_transform): V feeds the forward GEMM and the weight gradient, dM the weight gradient and
   // the adjoint-form input gradient, dX (transposed-conv form of the input gradient) its one GEMM
@@ -622,27 +649,129 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
   const bool pairD_ok = wslots && wgrad_pairs && (!(wadj && x.has_grad && y.has_grad) || wino_fwd_takes_pairs(Cop, Cip));
   const bool pairX_ok = wslots && wino_fwd_takes_pairs(Cop, Cip);
   const size_t kV = wslots ? reserve_k() : 0, kD = wslots ? reserve_k() : 0, kX = wslots ? reserve_k() : 0;
-  float* keepdM = nullptr;        // dM = A dY A^T, shared by the weight gradient (side stream) and the adjoint-form input gradient
-  if (wino && wadj && y.has_grad && x.has_grad && share_dy()) keepdM = static_cast<float*>(ctx.alloc((size_t)wP * wT * Cop * sizeof(float)));
-  if (wino) {
-    if (pcw) pcw_off = reserve_dgp(pcw_bs * wP);
-    else uf_off = reserve_dg(self, (size_t)wP * Cip * Cop);
-    wsV_need = std::max(wsV_need, std::max((size_t)wP * wT * std::max(Cip, Cop), (size_t)wP * wT2 * Cop));
-    wsM_need = std::max(wsM_need, std::max((size_t)wP * wT * std::max(Cip, Cop), (size_t)wP * wT2 * Cip));
-    wsU_need = std::max(wsU_need, (size_t)wP * Cip * Cop);
-  }
-  auto plane_view = [](float* p, size_t T, int C) {
-    TView v; v.p = p; v.N = 1; v.H = 1; v.W = (int)T; v.C = C; v.cs = C; return v;   // T x C matrix
+  // dM = A dY A^T, shared by the weight gradient (side stream) and the adjoint-form input gradient
+  float* keepdM = (wadj && y.has_grad && x.has_grad && share_dy()) ? static_cast<float*>(ctx.alloc((size_t)wP * wT * Cop * sizeof(float))) : nullptr;
+  const size_t pcw_off = pcw ? reserve_dgp(pcw_bs * wP) : 0, uf_off = pcw ? 0 : reserve_dg(self, (size_t)wP * Cip * Cop);
+  wsV_need = std::max(wsV_need, std::max((size_t)wP * wT * std::max(Cip, Cop), (size_t)wP * wT2 * Cop));
+  wsM_need = std::max(wsM_need, std::max((size_t)wP * wT * std::max(Cip, Cop), (size_t)wP * wT2 * Cip));
+  wsU_need = std::max(wsU_need, (size_t)wP * Cip * Cop);
+  // amax slot of the output buffer (round 5): the 6-point output transform folds its output's amax -- VGG16's conv + ReLU layers
+  // feed the next conv directly; everything else here is followed by a norm_act, which folds for its own output
+  const bool y_folds = actf != ACT_NONE && actf != ACT_TANH && wm != 2;
+  const size_t ySlot = note_writer(y.vbase, y_folds);
+  const float* xbase = x.vbase;
+  op.fwd = [=](Net& n) {
+    n.need(self);
+    float* V = keepV ? keepV : n.wsV;
+    const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
+    wino_input_transform(n.ctx.s, wm, wr, xv, 1, gf.pad_mode, wTh, wTw, V, wslots ? n.amax + slV : nullptr, xin, n.kscale + kV);
+    conv_fwd(n.ctx.s, plane_gemm(V, n.wsM, wT, Cip, Cop, Co, wP, plane_scale(xin != nullptr, n.kscale + kV, wslots ? n.amax + slV : nullptr),
+                                 {pcw ? nullptr : n.dg + uf_off, n.dgp + pcw_off, pcw, pcw_bs}));
+    wino_output_transform(n.ctx.s, wm, wr, n.wsM, Cop, wTh, wTw, bi >= 0 ? A->w + A->params[bi].off : nullptr, actf, yv, Co, 0,
+                          y_folds ? n.amax + ySlot : nullptr);
   };
+
+  // ---- backward plan
+  Var scratch;       // dR when an activation is fused into the epilogue
+  if (y.has_grad && actf != ACT_NONE) scratch = alloc_var(yv.N, yv.H, yv.W, Cop, false);
+  const bool want_dx = x.has_grad && y.has_grad;
+  // the input gradient's filters: U flipped and transposed (transposed-conv form) or with the channel axes swapped (adjoint form)
+  const int pcwt = (want_dx && wm != 2) ? wino_precut_tile(Cop, Cip) : 0;
+  const size_t pcwt_bs = pcwt ? conv_precut_elems(Cop, Cip, pcwt) : 0;
+  size_t pcwt_off = 0, ub_off = 0;
+  if (want_dx) {
+    if (pcwt) pcwt_off = reserve_dgp(pcwt_bs * wP);
+    else ub_off = reserve_dg(self, (size_t)wP * Cop * Cip);
+    op.grad_targets.push_back(x);
+  }
+  op.repack = [=](Net& n) {
+    const ParamDesc& wd = A->params[wi];
+    const float* wmax = nullptr;       // both directions transform the same packed parameter: one amax pass
+    if (pcw) wino_filter_transform_pc(n.ctx.s, wm, wr, wd.ws, 0, A->w + wd.off, pcw, n.dgp + pcw_off, pcw_bs, &wmax);
+    else wino_filter_transform(n.ctx.s, wm, wr, wd.ws, 0, A->w + wd.off, n.dg + uf_off);
+    if (want_dx) {
+      if (pcwt) wino_filter_transform_pc(n.ctx.s, wm, wr, wd.ws, wadj ? 2 : 1, A->w + wd.off, pcwt, n.dgp + pcwt_off, pcwt_bs, &wmax);
+      else wino_filter_transform(n.ctx.s, wm, wr, wd.ws, wadj ? 2 : 1, A->w + wd.off, n.dg + ub_off);
+    }
+  };
+  const TView ygv = y.g, xgv = x.g, scr = scratch.v;
+  const bool has_ygrad = y.has_grad;
+  const size_t scrSlot = (y.has_grad && actf != ACT_NONE) ? note_writer(scratch.v.p, true) : 0;      // (dY's amax: as in conv_direct)
+  const float* ygbase = y.gbase;
+  op.bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
+    if (!has_ygrad) return;
+    TView dY = ygv;
+    const float* dy_slot = nullptr;
+    if (actf != ACT_NONE) { act_bwd(n.ctx.s, ygv, yv, scr, actf, 0, n.amax + scrSlot); dY = scr; dy_slot = n.amax + scrSlot; }
+    else dy_slot = n.slot_if_complete(ygbase);
+    const ParamDesc& wd = A->params[wi];
+    const bool dx_now = want_dx && !(me.reads_net_input && !igrad);
+    // adjoint-form layers: the weight gradient and the input gradient multiply by the same dM planes -- transformed once, on the
+    // main stream, into the layer's own buffer (the side stream reads it while the main stream moves on)
+    const bool shared = keepdM && wgrad && dx_now;
+    const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
+    const float* din = pairD_ok ? dy_slot : nullptr;            // amax of dY bounds its planes
+    float* const slotV = wslots ? n.amax + slV : nullptr;
+    float* const slotD = wslots ? n.amax + slD : nullptr;
+    const PlaneScale dMs = plane_scale(din != nullptr, n.kscale + kD, slotD);
+    const PlanePanel Ut{pcwt ? nullptr : n.dg + ub_off, n.dgp + pcwt_off, pcwt, pcwt_bs};
+    if (shared) wino_dy_transform(n.ctx.s, wm, wr, dY, wTh, wTw, keepdM, slotD, din, n.kscale + kD);
+    if (wgrad) {
+      Stream& sw = n.wgrad_stream();          // dY is final: the weight-gradient work may run beside the dgrad chain
+      // dU[t] = V[t]^T dM[t] (wP batched reductions over the tiles), then dW = G^T dU G
+      float* V = keepV ? keepV : n.wsV;
+      float* dM = shared ? keepdM : n.wgrad_planes(sw);
+      if (!keepV) wino_input_transform(sw, wm, wr, xv, 1, gf.pad_mode, wTh, wTw, V, slotV, xin, n.kscale + kV);
+      if (!shared) wino_dy_transform(sw, wm, wr, dY, wTh, wTw, dM, slotD, din, n.kscale + kD);
+      conv_wgrad(sw, plane_wgrad(V, dM, n.wsU, wT, Cip, Cop, Co, wP, plane_scale(xin != nullptr, n.kscale + kV, slotV), dMs));
+      wino_filter_grad(sw, wm, wr, wd.ws, n.wsU, A->g + wd.off);
+      // (bias gradient on the main stream where no input gradient is formed: see conv_direct)
+      if (bi >= 0) n.bias_grad_of((!dx_now && bias_on_main()) ? n.ctx.s : sw, dY, A->g + A->params[bi].off);
+    }
+    if (!dx_now) return;
+    const int accf = me.acc.empty() ? 0 : me.acc[0];
+    if (!wadj) {
+      // input gradient = the transposed stride-1 conv over dY (flipped, channel-transposed filter)
+      const float* xdin = pairX_ok ? dy_slot : nullptr;
+      float* const slotX = wslots ? n.amax + slX : nullptr;
+      wino_input_transform(n.ctx.s, wm, wr, dY, wpad2, PAD_ZERO, wTh2, wTw2, n.wsV, slotX, xdin, n.kscale + kX);
+      conv_fwd(n.ctx.s, plane_gemm(n.wsV, n.wsM, wT2, Cop, Cip, Cip, wP, plane_scale(xdin != nullptr, n.kscale + kX, slotX), Ut));
+      wino_output_transform(n.ctx.s, wm, wr, n.wsM, Cip, wTh2, wTw2, nullptr, ACT_NONE, xgv, Cip, accf);
+      return;
+    }
+    // input gradient in the forward tiling: dM = A dY A^T, dV = dM U^T (U with the channel axes swapped), then the adjoint
+    // of the input transform scatters the patches BT^T dV BT back through the forward gather (padding rule included)
+    float* dMx = shared ? keepdM : n.wsV;
+    if (!shared) wino_dy_transform(n.ctx.s, wm, wr, dY, wTh, wTw, dMx, slotD, din, n.kscale + kD);
+    conv_fwd(n.ctx.s, plane_gemm(dMx, n.wsM, wT, Cop, Cip, Cip, wP, dMs, Ut));
+    wino_input_adjoint(n.ctx.s, wm, wr, n.wsM, Cip, 1, gf.pad_mode, wTh, wTw, xgv, accf);
+  };
+}
+
+// The direct kernels: the plain implicit GEMM, the folded tail conv, and the input gradient as a four-phase (k4 s2), stride-1
+// or reflect-folded forward-type launch over dY
+void Net::conv_direct(const ConvLayer& L, Op& op) {
+  const Var &x = L.x, &y = L.y;
+  const ConvKind kind = L.kind;
+  const int Co = L.Co, Cip = L.Cip, Cop = L.Cop, wi = L.wi, bi = L.bi, actf = L.actf, dgrad_C = L.dgrad_C;
+  ParamArena* A = &arena; Op* self = &op;
+  const Gather gf = L.geo.fwd;
+  const TView xv = x.v, yv = y.v;
+  const WShape& ws = arena.params[wi].ws;
+  // tail conv: run as 4 folded sub-pixel phases on the un-upsampled input (25 instead of 64
+  // taps per 2x2 outputs; see ops.h tail_fold_weights).  The folded weights and the folded
+  // weight-gradient scratch live next to the dgrad operands and follow arena.version.
+  const bool folded = kind == CK_TAIL_UP;
+  const size_t fe = folded ? tail_fold_offset(ws, 4) : 0;
+  const size_t fold_off = folded ? reserve_dg(self, fe) : 0, dfold_off = folded ? reserve_dg(self, fe) : 0;
   // weight panel pre-cut for the ring kernel (ops.h conv_precut): plain forward convs multiply by the arena weights themselves
-  const int Kf = KH * KH * Cip;
-  const int pc_f = (!wino && !folded) ? conv_precut_tile(Cip, arena.params[wi].ws.Npad) : 0;
-  const size_t pcf_off = pc_f ? reserve_dgp(conv_precut_elems(Kf, arena.params[wi].ws.Npad, pc_f)) : 0;
+  const int Kf = gf.KH * gf.KW * Cip;
+  const int pc_f = !folded ? conv_precut_tile(Cip, ws.Npad) : 0;
+  const size_t pcf_off = pc_f ? reserve_dgp(conv_precut_elems(Kf, ws.Npad, pc_f)) : 0;
   // amax slot of the output buffer: a direct conv with a fused activation feeds the next GEMM without a normalisation in
   // between (UNetDown without InstanceNorm, PatchGAN model.0), so it folds its output's amax (in the ring kernel's epilogue, else
   // by a pass: ops.h ConvFwdArgs::y_amax); everything else here is followed by a norm_act, which folds for its own output
-  // (round 5: the 6-point Winograd output transform folds too -- VGG16's conv + ReLU layers feed the next conv directly)
-  const bool y_folds = !folded && actf != ACT_NONE && actf != ACT_TANH && (!wino || wm != 2);
+  const bool y_folds = !folded && actf != ACT_NONE && actf != ACT_TANH;
   const size_t ySlot = note_writer(y.vbase, y_folds);
   const float* xbase = x.vbase;
   // Conv + InstanceNorm fusion: a plain direct conv above the register-resident InstanceNorm's 1024 pixels offers the
@@ -651,9 +780,9 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
   std::shared_ptr<bool> stat_use;
   {
     const int HoWo = yv.H * yv.W;
-    const bool stats_on = !(getenv("SWN_CONV_STATS") && atoi(getenv("SWN_CONV_STATS")) == 0);       // (A/B: read when a model is built)
-    const int chunk = (stats_on && !wino && !folded && pc_f == 128 && actf == ACT_NONE && HoWo > 1024 && yv.cs == yv.C && yv.p == y.vbase)
-                          ? conv_fwd_stat_chunk(Cip, arena.params[wi].ws.Npad, HoWo, yv.N, Kf) : 0;
+    const bool stats_on = env_on(getenv("SWN_CONV_STATS"));       // (A/B: read when a model is built)
+    const int chunk = (stats_on && pc_f == 128 && actf == ACT_NONE && HoWo > 1024 && yv.cs == yv.C && yv.p == y.vbase)
+                          ? conv_fwd_stat_chunk(Cip, ws.Npad, HoWo, yv.N, Kf) : 0;
     if (chunk) {
       const int chunks = HoWo / chunk;
       stat_partial = static_cast<double*>(ctx.alloc((size_t)yv.N * chunks * yv.C * 2 * sizeof(double)));
@@ -661,7 +790,7 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
       conv_stats[y.vbase] = StatLink{stat_partial, chunks, stat_use};
     }
   }
-  op->fwd = [=](Net& n) {
+  op.fwd = [=](Net& n) {
     const ParamDesc& wd = A->params[wi];
     ConvFwdArgs a;
     a.x = xv; a.g = gf; a.w = A->w + wd.off; a.Npad = wd.ws.Npad;
@@ -671,22 +800,6 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
     if (pc_f) { n.need(self); a.wpc = n.dgp + pcf_off; a.wpc_bn = pc_f; }
     a.bias = bi >= 0 ? A->w + A->params[bi].off : nullptr;
     a.act = actf; a.y = yv; a.Cout = Co;
-    if (wino) {
-      n.need(self);
-      float* V = keepV ? keepV : n.wsV;
-      const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
-      wino_input_transform(n.ctx.s, wm, wr, xv, 1, gf.pad_mode, wTh, wTw, V, wslots ? n.amax + slV : nullptr, xin, n.kscale + kV);
-      ConvFwdArgs g;
-      g.x = plane_view(V, wT, Cip); g.g.Ho = 1; g.g.Wo = (int)wT;
-      g.w = pcw ? nullptr : n.dg + uf_off; g.Npad = Cop; g.Cout = Co;
-      if (xin) g.x_pair_k = n.kscale + kV; else if (wslots) g.x_amax = n.amax + slV;
-      if (pcw) { g.wpc = n.dgp + pcw_off; g.wpc_bn = pcw; g.wpc_bs = pcw_bs; }
-      g.y = plane_view(n.wsM, wT, Cop);
-      g.batch = wP; g.x_bs = wT * Cip; g.w_bs = (size_t)Cip * Cop; g.y_bs = wT * Cop;
-      conv_fwd(n.ctx.s, g);
-      wino_output_transform(n.ctx.s, wm, wr, n.wsM, Cop, wTh, wTw, a.bias, actf, yv, Co, 0, y_folds ? n.amax + ySlot : nullptr);
-      return;
-    }
     if (!folded) { conv_fwd(n.ctx.s, a); return; }
     n.need(self);                            // folded weights are derived operands too
     a.x_amax = nullptr;
@@ -701,7 +814,7 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
   // tail conv: dR lives in a 32-channel buffer (pads stay zero) so that its input gradient -- a 5x5 stride-2 conv over dR with
   // K = 25 x Cop -- meets the ring kernel's 16-channel stages (K = 800 on the bf16-split ring kernel instead of K = 500 on the
   // register-staged f32-MFMA one)
-  const int CopD = (kind == CK_TAIL_UP && actf != ACT_NONE && Cop <= 32 && x.has_grad && conv_precut_tile(32, Cip) == 192) ? 32 : Cop;
+  const int CopD = (folded && actf != ACT_NONE && Cop <= 32 && x.has_grad && conv_precut_tile(32, Cip) == 192) ? 32 : Cop;
   if (y.has_grad && actf != ACT_NONE) scratch = alloc_var(yv.N, yv.H, yv.W, CopD, false);
   Var dxpad;
   int dg_mode = 0;
@@ -718,86 +831,45 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
   }
   gd.Ho = dHo; gd.Wo = dWo;
   const bool want_dx = x.has_grad && y.has_grad;
-  size_t dg_off = 0, pcd_off = 0;
-  int pc_d = 0, dpanels = 1, dKp = 0;
-  // the forward operand's weight amax, handed from the pc_f re-pack to the input-gradient operand's (ops.h conv_precut amax_io)
-  auto fwd_wmax = std::make_shared<const float*>(nullptr);
   // dgrad output channels = input buffer channels -- or, for a layer that reads a network input of which only the leading
   // channels are anyone's output (the generator's image inside the conditional discriminator's input), just those
-  const bool narrow_dx = dgrad_C > 0 && dgrad_C % 4 == 0 && dgrad_C < Cip && !wino && (kind == CK_K4S2 || kind == CK_K3S1_ZERO);
+  const bool narrow_dx = dgrad_C > 0 && dgrad_C % 4 == 0 && dgrad_C < Cip && (kind == CK_K4S2 || kind == CK_K3S1_ZERO);
   const int Ndg = narrow_dx ? dgrad_C : Cip;
-  const Var xg_target = narrow_dx ? x.slice(0, Ndg) : x;
+  // K4S2: four phase panels of 2x2 taps; stride-1: one panel of KH x KW taps over dY (Cop channels)
+  const int dpanels = kind == CK_K4S2 ? 4 : 1;
+  const int dKp = (kind == CK_K4S2 ? 4 : gd.KH * gd.KW) * CopD;
+  size_t dg_off = 0, pcd_off = 0;
+  int pc_d = 0;
   if (want_dx) {
-    if (wino) {
-      pcwt = wm != 2 ? wino_precut_tile(Cop, Cip) : 0;
-      pcwt_bs = pcwt ? conv_precut_elems(Cop, Cip, pcwt) : 0;
-      if (pcwt) pcwt_off = reserve_dgp(pcwt_bs * wP);
-      else ub_off = reserve_dg(self, (size_t)wP * Cop * Cip);
-    }
-    else dg_off = reserve_dg(self, dgrad_elems(arena.params[wi].ws, dg_mode, CopD, Ndg));
-    if (kind == CK_K3S1_REFLECT && !(wino && wadj)) dxpad = alloc_var(x.v.N, dHo, dWo, Cip, false);
-    op->grad_targets.push_back(xg_target);
-    if (!wino) {
-      // K4S2: four phase panels of 2x2 taps; stride-1: one panel of KH x KW taps over dY (Cop channels)
-      dpanels = kind == CK_K4S2 ? 4 : 1;
-      dKp = (kind == CK_K4S2 ? 4 : gd.KH * gd.KW) * CopD;
-      pc_d = conv_precut_tile(CopD, Ndg);
-      if (pc_d) pcd_off = reserve_dgp(conv_precut_elems(dKp, Ndg, pc_d) * dpanels);
-      const int pcd = pc_d, dK = dKp, dP = dpanels; const size_t pcdo = pcd_off;
-      op->repack = [=](Net& n) {
-        const ParamDesc& wd = A->params[wi];
+    dg_off = reserve_dg(self, dgrad_elems(ws, dg_mode, CopD, Ndg));
+    if (kind == CK_K3S1_REFLECT) dxpad = alloc_var(x.v.N, dHo, dWo, Cip, false);
+    op.grad_targets.push_back(narrow_dx ? x.slice(0, Ndg) : x);
+    pc_d = conv_precut_tile(CopD, Ndg);
+    if (pc_d) pcd_off = reserve_dgp(conv_precut_elems(dKp, Ndg, pc_d) * dpanels);
+  }
+  const size_t pcd_bs = pc_d ? conv_precut_elems(dKp, Ndg, pc_d) : 0;
+  if (pc_f || want_dx || folded)
+    op.repack = [=](Net& n) {
+      const ParamDesc& wd = A->params[wi];
+      // the forward operand first: the partial maxima its pre-cut takes are handed to the input-gradient operand's (ops.h
+      // conv_precut amax_io), which runs right behind it
+      const float* wmax = nullptr;
+      if (pc_f) conv_precut(n.ctx.s, A->w + wd.off, Kf, wd.ws.Npad, pc_f, 1, 0, n.dgp + pcf_off, &wmax);
+      if (want_dx) {
         repack_dgrad(n.ctx.s, wd.ws, dg_mode, CopD, Ndg, A->w + wd.off, n.dg + dg_off);
         // (the re-pack is a permutation of the parameter -- of its leading input channels if the gradient is narrow: the partial
         // maxima the forward operand's pre-cut just took, if it ran in front of us, bound it)
-        const float* wmax = *fwd_wmax;
-        if (pcd) conv_precut(n.ctx.s, n.dg + dg_off, dK, Ndg, pcd, dP, (size_t)dK * Ndg, n.dgp + pcdo, &wmax);
-        *fwd_wmax = nullptr;
-      };
-    }
-  }
-  if (wino) {
-    const bool wdx = want_dx;
-    const int pcwt_c = pcwt; const size_t pcwt_o = pcwt_off, pcwt_b = pcwt_bs;
-    op->repack = [=](Net& n) {
-      const ParamDesc& wd = A->params[wi];
-      const float* wmax = nullptr;       // both directions transform the same packed parameter: one amax pass
-      if (pcw) wino_filter_transform_pc(n.ctx.s, wm, wr, wd.ws, 0, A->w + wd.off, pcw, n.dgp + pcw_off, pcw_bs, &wmax);
-      else wino_filter_transform(n.ctx.s, wm, wr, wd.ws, 0, A->w + wd.off, n.dg + uf_off);
-      if (wdx) {
-        if (pcwt_c) wino_filter_transform_pc(n.ctx.s, wm, wr, wd.ws, wadj ? 2 : 1, A->w + wd.off, pcwt_c, n.dgp + pcwt_o, pcwt_b, &wmax);
-        else wino_filter_transform(n.ctx.s, wm, wr, wd.ws, wadj ? 2 : 1, A->w + wd.off, n.dg + ub_off);
+        if (pc_d) conv_precut(n.ctx.s, n.dg + dg_off, dKp, Ndg, pc_d, dpanels, (size_t)dKp * Ndg, n.dgp + pcd_off, &wmax);
       }
+      if (folded) tail_fold_weights(n.ctx.s, wd.ws, A->w + wd.off, n.dg + fold_off);
     };
-  }
-  if (folded) {
-    auto prev = op->repack;
-    op->repack = [=](Net& n) {
-      if (prev) prev(n);
-      const ParamDesc& wd = A->params[wi];
-      tail_fold_weights(n.ctx.s, wd.ws, A->w + wd.off, n.dg + fold_off);
-    };
-  }
-  if (pc_f) {
-    auto prev = op->repack;
-    op->repack = [=](Net& n) {
-      const ParamDesc& wd = A->params[wi];
-      const float* wmax = nullptr;
-      conv_precut(n.ctx.s, A->w + wd.off, Kf, wd.ws.Npad, pc_f, 1, 0, n.dgp + pcf_off, &wmax);     // forward operand first
-      // handed to the input-gradient operand's pre-cut -- only where that is the whole of `prev` (a folded / Winograd layer runs
-      // other amax passes in between, which reuse the scratch the partials live in)
-      *fwd_wmax = (!wino && !folded) ? wmax : nullptr;
-      if (prev) prev(n);
-      *fwd_wmax = nullptr;
-    };
-  }
-  const int pcd_k = pc_d; const size_t pcd_o = pcd_off, pcd_bs = pc_d ? conv_precut_elems(dKp, Ndg, pc_d) : 0;
   const TView ygv = y.g, xgv = narrow_dx ? x.g.slice(0, Ndg) : x.g, scr = CopD != Cop ? scratch.v.slice(0, Cop) : scratch.v, scr_full = scratch.v, dxp = dxpad.v;
   const bool has_ygrad = y.has_grad;
   // dY as a GEMM operand: dR from act_bwd (which folds its amax into the scratch buffer's slot) or y.g itself, whose slot --
   // if it has one -- the norm_act behind this conv fills in its backward
   const size_t scrSlot = (y.has_grad && actf != ACT_NONE) ? note_writer(scratch.v.p, true) : 0;
   const float* ygbase = y.gbase;
-  op->bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
+  op.bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
     if (!has_ygrad) return;
     TView dY = ygv;
     const float* dy_slot = nullptr;
@@ -805,33 +877,12 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
     else dy_slot = n.slot_if_complete(ygbase);
     const ParamDesc& wd = A->params[wi];
     const bool dx_now = want_dx && !(me.reads_net_input && !igrad);
-    // adjoint-form layers: the weight gradient and the input gradient multiply by the same dM planes -- transformed once, on the
-    // main stream, into the layer's own buffer (the side stream reads it while the main stream moves on)
-    const bool shared = keepdM && wino && wadj && wgrad && dx_now;
-    const float* xin = pairV_ok ? n.slot_if_complete(xbase) : nullptr;
-    const float* din = pairD_ok ? dy_slot : nullptr;            // amax of dY bounds its planes
-    if (shared) wino_dy_transform(n.ctx.s, wm, wr, dY, wTh, wTw, keepdM, wslots ? n.amax + slD : nullptr, din, n.kscale + kD);
     if (wgrad) {
       Stream& sw = n.wgrad_stream();          // dY is final: the weight-gradient work may run beside the dgrad chain
       ConvWgradArgs wa;
       wa.x = xv; wa.g = gf; wa.dy = dY; wa.dw = A->g + wd.off; wa.Npad = wd.ws.Npad; wa.Cout = Co;
       wa.x_amax = n.slot_if_complete(xbase); wa.dy_amax = dy_slot;
-      if (wino) {
-        // dU[t] = V[t]^T dM[t] (wP batched reductions over the tiles), then dW = G^T dU G
-        float* V = keepV ? keepV : n.wsV;
-        float* dM = shared ? keepdM : n.wgrad_planes(sw);
-        if (!keepV) wino_input_transform(sw, wm, wr, xv, 1, gf.pad_mode, wTh, wTw, V, wslots ? n.amax + slV : nullptr, xin, n.kscale + kV);
-        if (!shared) wino_dy_transform(sw, wm, wr, dY, wTh, wTw, dM, wslots ? n.amax + slD : nullptr, din, n.kscale + kD);
-        ConvWgradArgs g;
-        g.x = plane_view(V, wT, Cip); g.g.Ho = 1; g.g.Wo = (int)wT;
-        g.dy = plane_view(dM, wT, Cop);
-        g.dw = n.wsU; g.Npad = Cop; g.Cout = Co;
-        g.batch = wP; g.x_bs = wT * Cip; g.dy_bs = wT * Cop; g.dw_bs = (size_t)Cip * Cop;
-        if (xin) g.x_pair_k = n.kscale + kV; else if (wslots) g.x_amax = n.amax + slV;
-        if (din) g.dy_pair_k = n.kscale + kD; else if (wslots) g.dy_amax = n.amax + slD;
-        conv_wgrad(sw, g);
-        wino_filter_grad(sw, wm, wr, wd.ws, n.wsU, A->g + wd.off);
-      } else if (!folded) {
+      if (!folded) {
         conv_wgrad(sw, wa);
       } else {
         wa.x_amax = wa.dy_amax = nullptr;
@@ -844,190 +895,139 @@ void Net::conv(const std::string& name, const Var& x, const Var& y, ConvKind kin
       // bias gradient: beside the weight gradient on the second stream -- unless this layer forms no input gradient (the first layer of
       // a pass: PatchGAN's model.0 in backward_D, whose weight gradient is the step's exposed tail), where the main stream has nothing
       // else to do and the column sums run there, beside the weight gradient instead of behind it (round 6; same kernel, bit-identical)
-      static const bool bias_on_main = !(getenv("SWN_BIAS_MAIN") && atoi(getenv("SWN_BIAS_MAIN")) == 0);
-      if (bi >= 0) n.bias_grad_of((!dx_now && bias_on_main) ? n.ctx.s : sw, dY, A->g + A->params[bi].off);
+      if (bi >= 0) n.bias_grad_of((!dx_now && bias_on_main()) ? n.ctx.s : sw, dY, A->g + A->params[bi].off);
     }
     if (!dx_now) return;
     const int accf = me.acc.empty() ? 0 : me.acc[0];
-    if (wino && !wadj) {
-      // input gradient = the transposed stride-1 conv over dY (flipped, channel-transposed filter)
-      const float* xdin = pairX_ok ? dy_slot : nullptr;
-      wino_input_transform(n.ctx.s, wm, wr, dY, wpad2, PAD_ZERO, wTh2, wTw2, n.wsV, wslots ? n.amax + slX : nullptr, xdin, n.kscale + kX);
-      ConvFwdArgs g;
-      g.x = plane_view(n.wsV, wT2, Cop); g.g.Ho = 1; g.g.Wo = (int)wT2;
-      g.w = pcwt ? nullptr : n.dg + ub_off; g.Npad = Cip; g.Cout = Cip;
-      if (xdin) g.x_pair_k = n.kscale + kX; else if (wslots) g.x_amax = n.amax + slX;
-      if (pcwt) { g.wpc = n.dgp + pcwt_off; g.wpc_bn = pcwt; g.wpc_bs = pcwt_bs; }
-      g.y = plane_view(n.wsM, wT2, Cip);
-      g.batch = wP; g.x_bs = wT2 * Cop; g.w_bs = (size_t)Cop * Cip; g.y_bs = wT2 * Cip;
-      conv_fwd(n.ctx.s, g);
-      if (kind == CK_K3S1_REFLECT) {
-        wino_output_transform(n.ctx.s, wm, wr, n.wsM, Cip, wTh2, wTw2, nullptr, ACT_NONE, dxp, Cip, 0);
-        reflect_fold(n.ctx.s, dxp, xgv, accf);
-      } else {
-        wino_output_transform(n.ctx.s, wm, wr, n.wsM, Cip, wTh2, wTw2, nullptr, ACT_NONE, xgv, Cip, accf);
-      }
-      return;
-    }
-    if (wino) {
-      // input gradient in the forward tiling: dM = A dY A^T, dV = dM U^T (U with the channel axes swapped), then the adjoint
-      // of the input transform scatters the patches BT^T dV BT back through the forward gather (padding rule included)
-      float* dMx = shared ? keepdM : n.wsV;
-      if (!shared) wino_dy_transform(n.ctx.s, wm, wr, dY, wTh, wTw, dMx, wslots ? n.amax + slD : nullptr, din, n.kscale + kD);
-      ConvFwdArgs g;
-      g.x = plane_view(dMx, wT, Cop); g.g.Ho = 1; g.g.Wo = (int)wT;
-      g.w = pcwt ? nullptr : n.dg + ub_off; g.Npad = Cip; g.Cout = Cip;
-      if (din) g.x_pair_k = n.kscale + kD; else if (wslots) g.x_amax = n.amax + slD;
-      if (pcwt) { g.wpc = n.dgp + pcwt_off; g.wpc_bn = pcwt; g.wpc_bs = pcwt_bs; }
-      g.y = plane_view(n.wsM, wT, Cip);
-      g.batch = wP; g.x_bs = wT * Cop; g.w_bs = (size_t)Cop * Cip; g.y_bs = wT * Cip;
-      conv_fwd(n.ctx.s, g);
-      wino_input_adjoint(n.ctx.s, wm, wr, n.wsM, Cip, 1, gf.pad_mode, wTh, wTw, xgv, accf);
-      return;
-    }
+    ConvFwdArgs d;
+    d.w = n.dg + dg_off; d.Npad = Ndg; d.Cout = Ndg;
+    d.x_amax = dy_slot;
+    if (pc_d) { d.wpc = n.dgp + pcd_off; d.wpc_bn = pc_d; d.wpc_bs = pcd_bs; }
     if (kind == CK_K4S2) {
       // four sub-pixel phases of the transposed conv (2x2 taps each) in one launch
-      ConvFwdArgs d;
       d.x = dY; d.g.KH = d.g.KW = 2; d.g.stride = 1; d.g.pad_t = 1; d.g.pad_l = 1;
       d.g.Ho = dY.H; d.g.Wo = dY.W;
-      d.w = n.dg + dg_off; d.w_bs = (size_t)4 * Cop * Ndg; d.Npad = Ndg;
-      d.y = xgv; d.om.ymul = 2; d.om.xmul = 2; d.phases = 4; d.Cout = Ndg; d.accumulate = accf;
-      d.x_amax = dy_slot;
-      if (pcd_k) { d.wpc = n.dgp + pcd_o; d.wpc_bn = pcd_k; d.wpc_bs = pcd_bs; }
+      d.w_bs = (size_t)4 * Cop * Ndg;
+      d.y = xgv; d.om.ymul = 2; d.om.xmul = 2; d.phases = 4; d.accumulate = accf;
       conv_fwd(n.ctx.s, d);
+    } else if (kind == CK_K3S1_REFLECT) {
+      d.x = dY; d.g = gd; d.y = dxp; d.accumulate = 0;
+      conv_fwd(n.ctx.s, d);
+      reflect_fold(n.ctx.s, dxp, xgv, accf);
     } else {
-      ConvFwdArgs d;
-      d.x = CopD != Cop ? scr_full : dY; d.g = gd; d.w = n.dg + dg_off; d.Npad = Ndg; d.Cout = Ndg;
-      d.x_amax = dy_slot;
-      if (pcd_k) { d.wpc = n.dgp + pcd_o; d.wpc_bn = pcd_k; d.wpc_bs = pcd_bs; }
-      if (kind == CK_K3S1_REFLECT) {
-        d.y = dxp; d.accumulate = 0;
-        conv_fwd(n.ctx.s, d);
-        reflect_fold(n.ctx.s, dxp, xgv, accf);
-      } else {
-        d.y = xgv; d.accumulate = accf;
-        conv_fwd(n.ctx.s, d);
-      }
+      d.x = CopD != Cop ? scr_full : dY; d.g = gd; d.y = xgv; d.accumulate = accf;
+      conv_fwd(n.ctx.s, d);
     }
   };
-  ops.push_back(std::move(op));
 }
 
 // ---- ConvTranspose2d k4 s2 p1 (modules/layers.py:31, pix2pix_modules.py:226-246) ------
 void Net::convT(const std::string& name, const Var& x, const Var& y, int Co, bool bias) {
+  const WinoSwitches sw = wino_switches();
   if (y.v.H != x.v.H * 2 || y.v.W != x.v.W * 2) throw Error(1, "convT " + name + ": output view has the wrong size");
   const int Cip = x.v.C, Cop = round_up(Co, 4);
   if (y.v.C != Cop) throw Error(1, "convT " + name + ": output view must have round_up(Co,4) channels");
   const int wi = arena.add_weight(name + ".weight", WK_CONVT, Co, Cip, 4, 4, Cip, nullptr);
   const int bi = bias ? arena.add_bias(name + ".bias", Co) : -1;
   auto op = std::make_unique<Op>();
-  Op* self = op.get();
   op->label = name;
   op->param_off = arena.params[wi].off;
-  ParamArena* A = &arena;
-  const TView xv = x.v, yv = y.v, ygv = y.g, xgv = x.g;
   note_writer(y.vbase, false);        // (raw output: always followed by an InstanceNorm, never a GEMM operand itself)
-  const float* xbase = x.vbase; const float* ygbase = y.gbase;
+  const ConvLayer L{name, x, y, CK_K4S2, Cip, Co, Cip, Cop, wi, bi, ACT_NONE, ConvGeom(), false, 0};
   // enough channels: strided Winograd F(4x4,2x2) -- the transposed conv is the ADJOINT of a k4 s2 conv fine -> coarse, so its
   // forward is the coarse -> fine pipeline (dM = A x A^T, dV = dM U^T, adjoint polyphase transform) and its input gradient the
   // fine -> coarse one
-  if (s2_wino && s2_wino_wanted(Cop, Cip, x.v.H, x.v.W) && Co % 4 == 0) {
-    const int sP = 25, sTh = ceil_div(x.v.H, 4), sTw = ceil_div(x.v.W, 4), CV = 4 * Cop;
-    const size_t sT = (size_t)x.v.N * sTh * sTw;
-    const bool want_dx = x.has_grad && y.has_grad;
-    const size_t ut_off = reserve_dg(self, (size_t)sP * Cip * CV);                      // U^T[25][Cip][4 Cop]   (forward)
-    const size_t uf_off = want_dx ? reserve_dg(self, (size_t)sP * CV * Cip) : 0;        // U  [25][4 Cop][Cip]   (input gradient)
-    float* keepM = (keep_wino_inputs && y.has_grad) ? static_cast<float*>(ctx.alloc(sP * sT * Cip * sizeof(float))) : nullptr;
-    wsV_need = std::max(wsV_need, sP * sT * (size_t)std::max(CV, Cip));
-    wsM_need = std::max(wsM_need, sP * sT * (size_t)std::max(CV, Cip));
-    wsU_need = std::max(wsU_need, (size_t)sP * CV * Cip);
-    const int pct = conv_precut_tile(Cip, CV), pcf = want_dx ? conv_precut_tile(CV, Cip) : 0;
-    const size_t pct_bs = pct ? conv_precut_elems(Cip, CV, pct) : 0, pcf_bs = pcf ? conv_precut_elems(CV, Cip, pcf) : 0;
-    const size_t pct_off = pct ? reserve_dgp(pct_bs * sP) : 0, pcf_off = pcf ? reserve_dgp(pcf_bs * sP) : 0;
-    const size_t slM = reserve_slot(), slV = reserve_slot();     // amax of dM (planes of the coarse input) and of V (planes of dY, fine)
-    const bool wg_pairs = conv_wgrad_takes_pairs(sT, CV, Cip);
-    const bool pairM_ok = conv_fwd_takes_pairs(Cip, CV) && (!y.has_grad || wg_pairs);
-    const bool pairV_ok = wg_pairs && (!(x.has_grad && y.has_grad) || conv_fwd_takes_pairs(CV, Cip));
-    const size_t kM = reserve_k(), kVg = reserve_k();
-    // V = polyphase transform of dY serves the weight gradient (side stream) and the input gradient (main stream): one buffer per layer
-    float* keepVg = (y.has_grad && want_dx && share_dy()) ? static_cast<float*>(ctx.alloc(sP * sT * CV * sizeof(float))) : nullptr;
-    op->repack = [=](Net& n) {
-      const ParamDesc& wd = A->params[wi];
-      wino_s2_filter_transform(n.ctx.s, wd.ws, 1, A->w + wd.off, n.dg + ut_off);
-      const float* wmax = nullptr;
-      if (pct) conv_precut(n.ctx.s, n.dg + ut_off, Cip, CV, pct, sP, (size_t)Cip * CV, n.dgp + pct_off, &wmax);
-      if (want_dx) {
-        wino_s2_filter_transform(n.ctx.s, wd.ws, 0, A->w + wd.off, n.dg + uf_off);
-        if (pcf) conv_precut(n.ctx.s, n.dg + uf_off, CV, Cip, pcf, sP, (size_t)CV * Cip, n.dgp + pcf_off, &wmax);
-      }
-    };
-    op->fwd = [=](Net& n) {
-      n.need(self);
-      const ParamDesc& wd = A->params[wi];
-      (void)wd;
+  if (s2_wino && s2_wino_wanted(sw, Cop, Cip, x.v.H, x.v.W) && Co % 4 == 0) convT_wino_s2(L, *op);
+  else convT_direct(L, *op);
+  ops.push_back(std::move(op));
+}
+
+void Net::convT_wino_s2(const ConvLayer& L, Op& op) {
+  const Var &x = L.x, &y = L.y;
+  const int Cip = L.Cip, Cop = L.Cop, wi = L.wi, bi = L.bi;
+  ParamArena* A = &arena; Op* self = &op;
+  const TView xv = x.v, yv = y.v, ygv = y.g, xgv = x.g;
+  const float* xbase = x.vbase; const float* ygbase = y.gbase;
+  const int sP = 25, sTh = ceil_div(x.v.H, 4), sTw = ceil_div(x.v.W, 4), CV = 4 * Cop;
+  const size_t sT = (size_t)x.v.N * sTh * sTw;
+  const bool want_dx = x.has_grad && y.has_grad;
+  const size_t ut_off = reserve_dg(self, (size_t)sP * Cip * CV);                      // U^T[25][Cip][4 Cop]   (forward)
+  const size_t uf_off = want_dx ? reserve_dg(self, (size_t)sP * CV * Cip) : 0;        // U  [25][4 Cop][Cip]   (input gradient)
+  float* keepM = (keep_wino_inputs && y.has_grad) ? static_cast<float*>(ctx.alloc(sP * sT * Cip * sizeof(float))) : nullptr;
+  wsV_need = std::max(wsV_need, sP * sT * (size_t)std::max(CV, Cip));
+  wsM_need = std::max(wsM_need, sP * sT * (size_t)std::max(CV, Cip));
+  wsU_need = std::max(wsU_need, (size_t)sP * CV * Cip);
+  const int pct = conv_precut_tile(Cip, CV), pcf = want_dx ? conv_precut_tile(CV, Cip) : 0;
+  const size_t pct_bs = pct ? conv_precut_elems(Cip, CV, pct) : 0, pcf_bs = pcf ? conv_precut_elems(CV, Cip, pcf) : 0;
+  const size_t pct_off = pct ? reserve_dgp(pct_bs * sP) : 0, pcf_off = pcf ? reserve_dgp(pcf_bs * sP) : 0;
+  const size_t slM = reserve_slot(), slV = reserve_slot();     // amax of dM (planes of the coarse input) and of V (planes of dY, fine)
+  const bool wg_pairs = conv_wgrad_takes_pairs(sT, CV, Cip);
+  const bool pairM_ok = conv_fwd_takes_pairs(Cip, CV) && (!y.has_grad || wg_pairs);
+  const bool pairV_ok = wg_pairs && (!(x.has_grad && y.has_grad) || conv_fwd_takes_pairs(CV, Cip));
+  const size_t kM = reserve_k(), kVg = reserve_k();
+  // V = polyphase transform of dY serves the weight gradient (side stream) and the input gradient (main stream): one buffer per layer
+  float* keepVg = (y.has_grad && want_dx && share_dy()) ? static_cast<float*>(ctx.alloc(sP * sT * CV * sizeof(float))) : nullptr;
+  op.repack = [=](Net& n) {
+    const ParamDesc& wd = A->params[wi];
+    wino_s2_filter_transform(n.ctx.s, wd.ws, 1, A->w + wd.off, n.dg + ut_off);
+    const float* wmax = nullptr;
+    if (pct) conv_precut(n.ctx.s, n.dg + ut_off, Cip, CV, pct, sP, (size_t)Cip * CV, n.dgp + pct_off, &wmax);
+    if (want_dx) {
+      wino_s2_filter_transform(n.ctx.s, wd.ws, 0, A->w + wd.off, n.dg + uf_off);
+      if (pcf) conv_precut(n.ctx.s, n.dg + uf_off, CV, Cip, pcf, sP, (size_t)CV * Cip, n.dgp + pcf_off, &wmax);
+    }
+  };
+  op.fwd = [=](Net& n) {
+    n.need(self);
+    float* dM = keepM ? keepM : n.wsV;
+    const float* xin = pairM_ok ? n.slot_if_complete(xbase) : nullptr;
+    wino_dy_transform(n.ctx.s, 4, 2, xv, sTh, sTw, dM, n.amax + slM, xin, n.kscale + kM);
+    conv_fwd(n.ctx.s, plane_gemm(dM, n.wsM, sT, Cip, CV, CV, sP, plane_scale(xin != nullptr, n.kscale + kM, n.amax + slM),
+                                 {n.dg + ut_off, n.dgp + pct_off, pct, pct_bs}));
+    wino_s2_input_adjoint(n.ctx.s, n.wsM, Cop, sTh, sTw, yv, bi >= 0 ? A->w + A->params[bi].off : nullptr, 0);
+  };
+  if (want_dx) op.grad_targets.push_back(x);
+  const bool has_ygrad = y.has_grad;
+  op.bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
+    if (!has_ygrad) return;
+    const ParamDesc& wd = A->params[wi];
+    const bool dx_now = want_dx && !(me.reads_net_input && !igrad);
+    const bool shared = keepVg && wgrad && dx_now;
+    const float* xin = pairM_ok ? n.slot_if_complete(xbase) : nullptr;
+    const float* din = pairV_ok ? n.slot_if_complete(ygbase) : nullptr;
+    const PlaneScale Vs = plane_scale(din != nullptr, n.kscale + kVg, n.amax + slV);
+    if (shared) wino_s2_input_transform(n.ctx.s, ygv, sTh, sTw, keepVg, n.amax + slV, din, n.kscale + kVg);
+    if (wgrad) {
+      // dU[25][4 Cop][Cip] = V(dY fine)^T dM(x coarse)
+      Stream& sw = n.wgrad_stream();
+      float* V = shared ? keepVg : n.wgrad_planes(sw);
       float* dM = keepM ? keepM : n.wsV;
-      const float* xin = pairM_ok ? n.slot_if_complete(xbase) : nullptr;
-      wino_dy_transform(n.ctx.s, 4, 2, xv, sTh, sTw, dM, n.amax + slM, xin, n.kscale + kM);
-      ConvFwdArgs g;
-      g.x = plane_mat(dM, sT, Cip); g.g.Ho = 1; g.g.Wo = (int)sT;
-      g.w = n.dg + ut_off; g.Npad = CV; g.Cout = CV;
-      g.y = plane_mat(n.wsM, sT, CV);
-      g.batch = sP; g.x_bs = sT * Cip; g.w_bs = (size_t)Cip * CV; g.y_bs = sT * CV;
-      if (xin) g.x_pair_k = n.kscale + kM; else g.x_amax = n.amax + slM;
-      if (pct) { g.wpc = n.dgp + pct_off; g.wpc_bn = pct; g.wpc_bs = pct_bs; }
-      conv_fwd(n.ctx.s, g);
-      wino_s2_input_adjoint(n.ctx.s, n.wsM, Cop, sTh, sTw, yv, bi >= 0 ? A->w + A->params[bi].off : nullptr, 0);
-    };
-    if (want_dx) op->grad_targets.push_back(x);
-    const bool has_ygrad = y.has_grad;
-    op->bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
-      if (!has_ygrad) return;
-      const ParamDesc& wd = A->params[wi];
-      const bool dx_now = want_dx && !(me.reads_net_input && !igrad);
-      const bool shared = keepVg && wgrad && dx_now;
-      const float* xin = pairM_ok ? n.slot_if_complete(xbase) : nullptr;
-      const float* din = pairV_ok ? n.slot_if_complete(ygbase) : nullptr;
-      if (shared) wino_s2_input_transform(n.ctx.s, ygv, sTh, sTw, keepVg, n.amax + slV, din, n.kscale + kVg);
-      if (wgrad) {
-        // dU[25][4 Cop][Cip] = V(dY fine)^T dM(x coarse)
-        Stream& sw = n.wgrad_stream();
-        float* V = shared ? keepVg : n.wgrad_planes(sw);
-        float* dM = keepM ? keepM : n.wsV;
-        if (!shared) wino_s2_input_transform(sw, ygv, sTh, sTw, V, n.amax + slV, din, n.kscale + kVg);
-        if (!keepM) wino_dy_transform(sw, 4, 2, xv, sTh, sTw, dM, n.amax + slM, xin, n.kscale + kM);
-        ConvWgradArgs g;
-        g.x = plane_mat(V, sT, CV); g.g.Ho = 1; g.g.Wo = (int)sT;
-        g.dy = plane_mat(dM, sT, Cip);
-        g.dw = n.wsU; g.Npad = Cip; g.Cout = Cip;
-        g.batch = sP; g.x_bs = sT * CV; g.dy_bs = sT * Cip; g.dw_bs = (size_t)CV * Cip;
-        if (din) g.x_pair_k = n.kscale + kVg; else g.x_amax = n.amax + slV;
-        if (xin) g.dy_pair_k = n.kscale + kM; else g.dy_amax = n.amax + slM;
-        conv_wgrad(sw, g);
-        wino_s2_filter_grad(sw, wd.ws, n.wsU, A->g + wd.off);
-        if (bi >= 0) n.bias_grad_of(sw, ygv, A->g + A->params[bi].off);
-      }
-      if (!dx_now) return;
-      float* Vx = shared ? keepVg : n.wsV;
-      if (!shared) wino_s2_input_transform(n.ctx.s, ygv, sTh, sTw, Vx, n.amax + slV, din, n.kscale + kVg);
-      ConvFwdArgs g;
-      g.x = plane_mat(Vx, sT, CV); g.g.Ho = 1; g.g.Wo = (int)sT;
-      g.w = n.dg + uf_off; g.Npad = Cip; g.Cout = Cip;
-      g.y = plane_mat(n.wsM, sT, Cip);
-      g.batch = sP; g.x_bs = sT * CV; g.w_bs = (size_t)CV * Cip; g.y_bs = sT * Cip;
-      if (din) g.x_pair_k = n.kscale + kVg; else g.x_amax = n.amax + slV;
-      if (pcf) { g.wpc = n.dgp + pcf_off; g.wpc_bn = pcf; g.wpc_bs = pcf_bs; }
-      conv_fwd(n.ctx.s, g);
-      wino_output_transform(n.ctx.s, 4, 2, n.wsM, Cip, sTh, sTw, nullptr, ACT_NONE, xgv, Cip, me.acc.empty() ? 0 : me.acc[0]);
-    };
-    ops.push_back(std::move(op));
-    return;
-  }
+      if (!shared) wino_s2_input_transform(sw, ygv, sTh, sTw, V, n.amax + slV, din, n.kscale + kVg);
+      if (!keepM) wino_dy_transform(sw, 4, 2, xv, sTh, sTw, dM, n.amax + slM, xin, n.kscale + kM);
+      conv_wgrad(sw, plane_wgrad(V, dM, n.wsU, sT, CV, Cip, Cip, sP, Vs, plane_scale(xin != nullptr, n.kscale + kM, n.amax + slM)));
+      wino_s2_filter_grad(sw, wd.ws, n.wsU, A->g + wd.off);
+      if (bi >= 0) n.bias_grad_of(sw, ygv, A->g + A->params[bi].off);
+    }
+    if (!dx_now) return;
+    float* Vx = shared ? keepVg : n.wsV;
+    if (!shared) wino_s2_input_transform(n.ctx.s, ygv, sTh, sTw, Vx, n.amax + slV, din, n.kscale + kVg);
+    conv_fwd(n.ctx.s, plane_gemm(Vx, n.wsM, sT, CV, Cip, Cip, sP, Vs, {n.dg + uf_off, n.dgp + pcf_off, pcf, pcf_bs}));
+    wino_output_transform(n.ctx.s, 4, 2, n.wsM, Cip, sTh, sTw, nullptr, ACT_NONE, xgv, Cip, me.acc.empty() ? 0 : me.acc[0]);
+  };
+}
+
+void Net::convT_direct(const ConvLayer& L, Op& op) {
+  const Var &x = L.x, &y = L.y;
+  const int Co = L.Co, Cip = L.Cip, Cop = L.Cop, wi = L.wi, bi = L.bi;
+  ParamArena* A = &arena; Op* self = &op;
+  const TView xv = x.v, yv = y.v, ygv = y.g, xgv = x.g;
+  const float* xbase = x.vbase; const float* ygbase = y.gbase;
   const size_t phase_elems = (size_t)4 * Cip * round_up(Co, 4);
   // pre-cut panels for the ring kernel: the four forward phase panels (arena layout) and the k4 s2 input-gradient operand
   const int pc_f = conv_precut_tile(Cip, Cop);
   const size_t pcf_bs = pc_f ? conv_precut_elems(4 * Cip, Cop, pc_f) : 0;
   const size_t pcf_off = pc_f ? reserve_dgp(pcf_bs * 4) : 0;
-  op->fwd = [=](Net& n) {
+  op.fwd = [=](Net& n) {
     const ParamDesc& wd = A->params[wi];
     ConvFwdArgs f;                          // 4 sub-pixel phases (2x2 taps each), one launch
     if (pc_f) { n.need(self); f.wpc = n.dgp + pcf_off; f.wpc_bn = pc_f; f.wpc_bs = pcf_bs; }
@@ -1044,10 +1044,10 @@ void Net::convT(const std::string& name, const Var& x, const Var& y, int Co, boo
   if (want_dx) {
     dg_off = reserve_dg(self, dgrad_elems(arena.params[wi].ws, 2, Cop, Cip));
     if (pc_d) pcd_off = reserve_dgp(conv_precut_elems(16 * Cop, Cip, pc_d));
-    op->grad_targets.push_back(x);
+    op.grad_targets.push_back(x);
   }
   if (want_dx || pc_f)
-    op->repack = [=](Net& n) {
+    op.repack = [=](Net& n) {
       const ParamDesc& wd = A->params[wi];
       const float* wmax = nullptr;       // the k4 s2 re-pack permutes the four phase panels: one amax pass
       if (pc_f) conv_precut(n.ctx.s, A->w + wd.off, 4 * Cip, Cop, pc_f, 4, phase_elems, n.dgp + pcf_off, &wmax);
@@ -1057,7 +1057,7 @@ void Net::convT(const std::string& name, const Var& x, const Var& y, int Co, boo
       }
     };
   const bool has_ygrad = y.has_grad;
-  op->bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
+  op.bwd = [=](Net& n, Op& me, bool wgrad, bool igrad) {
     if (!has_ygrad) return;
     const ParamDesc& wd = A->params[wi];
     if (wgrad) {
@@ -1079,7 +1079,6 @@ void Net::convT(const std::string& name, const Var& x, const Var& y, int Co, boo
     if (pc_d) { d.wpc = n.dgp + pcd_off; d.wpc_bn = pc_d; }
     conv_fwd(n.ctx.s, d);
   };
-  ops.push_back(std::move(op));
 }
 
 // ---- [InstanceNorm] -> act -> [dropout] (+ residual) -----------------------------------
@@ -1248,11 +1247,7 @@ void Net::finalize(const std::vector<Var>& pre) {
   finalized_ = true;
 }
 
-// SWN_SHARE_DY=0: the weight gradient transforms dY for itself on the side stream (the round-3 behaviour); read once
-bool Net::share_dy() const {
-  static const bool on = true;
-  return on && keep_wino_inputs && ctx.has_side;
-}
+bool Net::share_dy() const { return keep_wino_inputs && ctx.has_side; }
 void Net::forward() {
   if (!finalized_) throw Error(1, "Net::forward before finalize");
   if (amax) dev_memset(ctx.s, amax, 0, amax_n * sizeof(float));       // every slot: the step's producers fold into zeros
@@ -1282,11 +1277,11 @@ void Net::forward_from(int op_begin) {
 // further down: both queues are fed in the order the GPU consumes them.  SWN_PREFETCH=3: everything at the top (the old order, for the
 // A/B); 0: in order on the main stream.
 int Net::prefetch_mode() {
-  static const int mode = getenv("SWN_PREFETCH") ? atoi(getenv("SWN_PREFETCH")) : 1;
+  static const int mode = env_int(getenv("SWN_PREFETCH"), 1);
   return mode;
 }
 static size_t prefetch_ahead() {
-  static const int n = getenv("SWN_PREFETCH_AHEAD") ? std::max(1, atoi(getenv("SWN_PREFETCH_AHEAD"))) : 4;
+  static const int n = std::max(1, env_int(getenv("SWN_PREFETCH_AHEAD"), 4));
   return (size_t)n;
 }
 void Net::prefetch_dgrad() {
@@ -1558,8 +1553,7 @@ void Model::step_captured(const float labels[3], bool training, uint64_t seed) {
     return;
   }
   // a recorded sequence bakes in what is not in StepParams: one stream or two, and where AdamW sits (round-4 advice)
-  const char* am = getenv("SWN_STREAM_ADAMW");
-  const int key = (ctx->use_side() ? 1 : 0) | ((am ? atoi(am) : 1) << 1);
+  const int key = (ctx->use_side() ? 1 : 0) | (env_int(getenv("SWN_STREAM_ADAMW"), 1) << 1);
   if (step_graph_[gi] && step_graph_key_[gi] != key) { graph_destroy(step_graph_[gi]); step_graph_[gi] = nullptr; }
   if (!step_graph_[gi]) {
     step_graph_key_[gi] = key;
@@ -1625,8 +1619,7 @@ void Model::step(const float labels[3], bool training, uint64_t seed) {
   }
   // SWN_STREAM_ADAMW=0: AdamW as one launch behind the whole backward pass; 2: the bucketed order also without a side stream
   // (what the host simulator can exercise).  Read per step.
-  const char* e = getenv("SWN_STREAM_ADAMW");
-  const int mode = e ? atoi(e) : 1;
+  const int mode = env_int(getenv("SWN_STREAM_ADAMW"), 1);
   if (mode == 2 || (mode != 0 && ctx->use_side())) {
     backward_G_streamed(labels[2]);
     return;

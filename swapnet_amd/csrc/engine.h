@@ -2,6 +2,7 @@
 // NHWC views, and the network builders for the SwapNet hot path.  Host C++ only; every
 // device action goes through ops.h.
 #pragma once
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <memory>
@@ -11,6 +12,11 @@
 #include "ops.h"
 
 namespace swn {
+
+// SWN_* switches, from the value getenv() returned: on unless set to 0 / an integer with a default.  The getenv("SWN_...")
+// itself stays at the call site: when it runs is part of each switch's contract (tests/test_route_switches.py)
+inline bool env_on(const char* v) { return !(v && atoi(v) == 0); }
+inline int env_int(const char* v, int dflt) { return v ? atoi(v) : dflt; }
 
 struct Ctx {
   Stream s;
@@ -275,6 +281,15 @@ class Net {
  private:
   size_t reserve_dg(Op* op, size_t elems);
   bool finalized_ = false;
+  // conv() / convT() choose a route per layer; one builder per route plans the layer's buffers and its three closures (engine.cpp)
+  struct ConvLayer;
+  void conv_head_tapn(const ConvLayer& L, Op& op);
+  void conv_wino_s2(const ConvLayer& L, Op& op);
+  void conv_tail_wino(const ConvLayer& L, Op& op);
+  void conv_wino_s1(const ConvLayer& L, int wm, Op& op);
+  void conv_direct(const ConvLayer& L, Op& op);
+  void convT_wino_s2(const ConvLayer& L, Op& op);
+  void convT_direct(const ConvLayer& L, Op& op);
 };
 
 // ---- network builders (reference layouts in the .cpp) ----------------------------------

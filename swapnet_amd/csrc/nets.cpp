@@ -238,7 +238,7 @@ class WarpModel final : public Model {
       // PatchGAN's input gradient then accumulates into it (the planner is told the range is pre-written).  a + b = b + a: the sum is
       // bit-identical to the old order (GAN term written, CE accumulated).  Only where the first layer's gradient covers exactly
       // the generator's channels (the narrow input gradient); SWN_CE_EARLY=0 keeps the old order (read when a model is built).
-      const bool ce_early_wanted = !(getenv("SWN_CE_EARLY") && atoi(getenv("SWN_CE_EARLY")) == 0);
+      const bool ce_early_wanted = env_on(getenv("SWN_CE_EARLY"));
       ce_first_ = false;
       if (ce_early_wanted)
         for (auto& op : D1->ops)

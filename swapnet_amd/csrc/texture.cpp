@@ -150,7 +150,7 @@ class TextureModel final : public Model {
     AllocScope mine(c, owned_allocs);
     G = std::make_unique<Net>(c, arenaG);
     G->keep_wino_inputs = train;
-    G->s2_wino = getenv("SWN_WINO_S2") && atoi(getenv("SWN_WINO_S2")) == 2;
+    G->s2_wino = env_int(getenv("SWN_WINO_S2"), 0) == 2;
     tex = G->alloc_var(B, H, W, 4, false);
     // first-layer buffers padded to multiples of 16 channels (zero pads meeting zero weight rows): 56 -> 64, 24 -> 32 and, for
     // VGG16's conv1_1, 4 -> 16 put those layers on the ring kernels (nets.cpp ring_pad; SWN_FIRST_RING=0: the round-3 layout)
@@ -313,7 +313,7 @@ class TextureModel final : public Model {
     else { wgan_loss(s, pf, 1.f, gs, losses + L_D_FAKE, &gf); wgan_loss(s, pr, -1.f, gs, losses + L_D_REAL, &gr); }
     scalar_axpby(s, losses + L_D_FAKE, 0.5f, losses + L_D_REAL, 0.5f, losses + L_D);
     D2->backward_range(true, false, 0, (int)D2->ops.size(), /*join=*/false);
-    static const bool vt_early = !(getenv("SWN_VT_EARLY") && atoi(getenv("SWN_VT_EARLY")) == 0);
+    static const bool vt_early = env_on(getenv("SWN_VT_EARLY"));
     if (vt_early && VT && (hyper.lambda_content != 0.f || hyper.lambda_style != 0.f)) {
       VF->refresh_dgrad();                 // (the frozen VGG16's operands: derived once)
       VT->forward();
