@@ -145,6 +145,15 @@ int swn_model_param_set(swn_model* m, int net, int which, const char* name, cons
 int swn_model_param_get(swn_model* m, int net, int which, const char* name, float* dev_dst);
 int swn_model_optim_step_get(swn_model* m, int net, int* step);   /* AdamW `step` counter */
 int swn_model_optim_step_set(swn_model* m, int net, int step);
+/* The optimizer of one network, optimizers.define_optimizer's choice (optimizers/__init__.py:37-60): kind 0 = AdamW (the default
+ * of every model), 1 = AdaBound (Luo et al., ICLR 2019, as adabound 0.0.5 executes it with amsbound off and eps 1e-8).  AdaBound
+ * reads lr, betas and weight decay from swn_hyper like AdamW -- the decay as a COUPLED L2 term, g += wd * p -- and clamps the
+ * per-element rate lr * sqrt(1 - b2^t) / (1 - b1^t) / (sqrt(v) + eps) to final * [1 - 1/(gamma t + 1), 1 + 1/(gamma t)],
+ * final = final_lr * lr / base_lr; base_lr = the lr the optimizer was constructed with (> 0), gamma > 0 (package default 1e-3).
+ * The three values are ignored for kind 0.  Moments and the step counter are kept (which 2 / 3, swn_model_optim_step_*).  Models
+ * sharing the arenas share the choice.  Drops the model's recorded step graphs when anything changes.  HIP library only: the
+ * CI simulator refuses kind 1. */
+int swn_model_set_optimizer(swn_model* m, int net, int kind, float final_lr, float base_lr, float gamma);
 
 /* BaseModel.set_input (models/warp_model.py:99-104, models/texture_model.py:113-119).
  * warp slots: 0 bodys (B,3,H,W), 1 input_cloths (B,19,H,W), 2 target_cloths (B,19,H,W)
@@ -325,6 +334,10 @@ int swn_op_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const fl
 /* torch.optim.AdamW single step on flat arrays (optimizers/__init__.py:52-59) */
 int swn_op_adamw(swn_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2,
                  float eps, float wd, int step);
+/* adabound.AdaBound single step on flat arrays (optimizers/__init__.py:37-60; the update swn_model_set_optimizer describes),
+ * n % 4 == 0, step = 1-based.  HIP library only. */
+int swn_op_adabound(swn_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2,
+                    float eps, float wd, float final_lr, float base_lr, float gamma, int step);
 
 #ifdef __cplusplus
 }

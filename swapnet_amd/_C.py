@@ -57,6 +57,7 @@ _PROTOS = {
     "swn_model_param_get": ([_vp, _i, _i, C.c_char_p, _fp], _i),
     "swn_model_optim_step_get": ([_vp, _i, C.POINTER(_i)], _i),
     "swn_model_optim_step_set": ([_vp, _i, _i], _i),
+    "swn_model_set_optimizer": ([_vp, _i, _i, _f, _f, _f], _i),
     "swn_model_set_input": ([_vp, _i, _fp, _i, _i, _i, _i], _i),
     "swn_model_set_input_labels": ([_vp, _i, _vp, _i, _i, _i], _i),
     "swn_model_get_output": ([_vp, _i, _fp], _i),
@@ -102,6 +103,7 @@ _PROTOS = {
     "swn_op_norm_act_bwd2": ([_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp], _i),
     "swn_op_norm_act_dropout": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, C.c_uint64, _fp, _fp, _fp], _i),
     "swn_op_adamw": ([_vp, _fp, _fp, _fp, _fp, C.c_size_t, _f, _f, _f, _f, _f, _i], _i),
+    "swn_op_adabound": ([_vp, _fp, _fp, _fp, _fp, C.c_size_t, _f, _f, _f, _f, _f, _f, _f, _f, _i], _i),
 }
 
 

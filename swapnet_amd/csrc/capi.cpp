@@ -218,6 +218,25 @@ static ParamArena& arena_of(swn_model* m, int net) {
   return *a;
 }
 
+int swn_model_set_optimizer(swn_model* m, int net, int kind, float final_lr, float base_lr, float gamma) {
+  return guard([&] {
+    REQUIRE(net == 0 || net == 1, "optimizers exist for the generator (0) and the discriminator (1)");
+    ParamArena& a = arena_of(m, net);
+    REQUIRE(m->m->is_train, "the model was created without optimizers (is_train = 0)");
+    REQUIRE(kind == OPT_ADAMW || kind == OPT_ADABOUND, "optimizer kind not implemented (0 AdamW, 1 AdaBound)");
+    if (kind == OPT_ADABOUND) {
+      // the simulator's update is AdamW whatever the kind says: refuse here, not at the first step
+      if (!is_device_build()) throw Error(1, "swn_model_set_optimizer: AdaBound is not implemented on the host simulator (HIP kernel only)");
+      REQUIRE(final_lr >= 0.f && base_lr > 0.f && gamma > 0.f, "AdaBound needs final_lr >= 0, base_lr > 0, gamma > 0");
+    }
+    // a recorded step (swn_model_step_captured) launches the kernel of the kind it was recorded with
+    if (a.opt_kind != kind || (kind == OPT_ADABOUND && (a.final_lr != final_lr || a.base_lr != base_lr || a.gamma != gamma)))
+      m->m->invalidate_step_graphs();
+    a.opt_kind = kind;
+    if (kind == OPT_ADABOUND) { a.final_lr = final_lr; a.base_lr = base_lr; a.gamma = gamma; }
+  });
+}
+
 int swn_model_param_count(swn_model* m, int net, int* out) {
   return guard([&] { REQUIRE(out, "NULL"); *out = (int)arena_of(m, net).params.size(); });
 }
@@ -685,6 +704,18 @@ int swn_op_adamw(swn_ctx* ctx, float* p, const float* g, float* m, float* v, siz
   return guard([&] {
     REQUIRE(ctx && p && g && m && v, "NULL argument");
     AdamWArgs a{p, g, m, v, n, lr, b1, b2, eps, wd, step};
+    adamw_step(ctx->c->s, a);
+    stream_sync(ctx->c->s);
+  });
+}
+int swn_op_adabound(swn_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2,
+                    float eps, float wd, float final_lr, float base_lr, float gamma, int step) {
+  return guard([&] {
+    REQUIRE(ctx && p && g && m && v, "NULL argument");
+    REQUIRE(step >= 1 && base_lr > 0.f && gamma > 0.f, "AdaBound needs step >= 1, base_lr > 0, gamma > 0");
+    if (!is_device_build()) throw Error(1, "swn_op_adabound: AdaBound is not implemented on the host simulator (HIP kernel only)");
+    AdamWArgs a{p, g, m, v, n, lr, b1, b2, eps, wd, step};
+    a.kind = OPT_ADABOUND; a.final_lr = final_lr; a.base_lr = base_lr; a.gamma = gamma;
     adamw_step(ctx->c->s, a);
     stream_sync(ctx->c->s);
   });

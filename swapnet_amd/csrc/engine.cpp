@@ -1408,15 +1408,31 @@ void Model::backward_G_part(float label_real, int part, size_t* ready_off, size_
 }
 
 // ---------------------------------------------------------------------------------------
-void Model::optimizer_step(int net) {
-  ParamArena& A = arena(net);
-  A.step += 1;
-  AdamWArgs a;
-  a.p = A.w; a.g = A.g; a.m = A.m; a.v = A.v; a.n = A.n;
+AdamWArgs Model::optimizer_args(int net) {
+  const ParamArena& A = arena(net);
+  AdamWArgs a{};
   a.lr = net == 0 ? hyper.lr : hyper.d_lr;
   a.weight_decay = net == 0 ? hyper.weight_decay : hyper.d_weight_decay;
-  a.beta1 = net == 0 ? hyper.b1 : hyper.d_b1; a.beta2 = net == 0 ? hyper.b2 : hyper.d_b2; a.eps = 1e-8f; a.step = A.step;
-  if (indirect) a.sched_dev = net == 0 ? reinterpret_cast<const float*>(sp_dev) + 6 : reinterpret_cast<const float*>(sp_dev) + 8;
+  a.beta1 = net == 0 ? hyper.b1 : hyper.d_b1; a.beta2 = net == 0 ? hyper.b2 : hyper.d_b2; a.eps = 1e-8f;
+  a.kind = A.opt_kind;
+  if (a.kind == OPT_ADAMW) {
+    if (indirect) a.sched_dev = net == 0 ? sp_dev->schedG : sp_dev->schedD;
+    return a;
+  }
+  if (a.kind != OPT_ADABOUND) throw Error(1, "optimizer_step: unknown optimizer kind");
+  // the simulator's adamw_step knows AdamW only and would apply it whatever `kind` says
+  if (!is_device_build()) throw Error(1, "optimizer_step: AdaBound is not implemented on the host simulator (HIP kernel only)");
+  a.final_lr = A.final_lr; a.base_lr = A.base_lr; a.gamma = A.gamma;
+  if (indirect) a.sched_dev = net == 0 ? sp_dev->boundG : sp_dev->boundD;
+  return a;
+}
+
+void Model::optimizer_step(int net) {
+  ParamArena& A = arena(net);
+  AdamWArgs a = optimizer_args(net);
+  A.step += 1;
+  a.p = A.w; a.g = A.g; a.m = A.m; a.v = A.v; a.n = A.n;
+  a.step = A.step;
   adamw_step(ctx->s, a);
   A.version += 1;
 }
@@ -1501,14 +1517,11 @@ void Model::optimizer_step_range(int net, size_t off, size_t count, int first) {
 void Model::optimizer_step_range_on(Stream& st, int net, size_t off, size_t count, int first) {
   ParamArena& A = arena(net);
   if (off % 4 || off + count > A.n) throw Error(1, "optimizer_step_range: range outside the arena / not 16-byte aligned");
+  AdamWArgs a = optimizer_args(net);
   if (first) A.step += 1;
   if (count == 0) return;
-  AdamWArgs a;
   a.p = A.w + off; a.g = A.g + off; a.m = A.m + off; a.v = A.v + off; a.n = (count + 3) / 4 * 4 <= A.n - off ? (count + 3) / 4 * 4 : count;
-  a.lr = net == 0 ? hyper.lr : hyper.d_lr;
-  a.weight_decay = net == 0 ? hyper.weight_decay : hyper.d_weight_decay;
-  a.beta1 = net == 0 ? hyper.b1 : hyper.d_b1; a.beta2 = net == 0 ? hyper.b2 : hyper.d_b2; a.eps = 1e-8f; a.step = A.step;
-  if (indirect) a.sched_dev = net == 0 ? reinterpret_cast<const float*>(sp_dev) + 6 : reinterpret_cast<const float*>(sp_dev) + 8;
+  a.step = A.step;
   adamw_step(st, a);
   A.version += 1;
 }
@@ -1531,7 +1544,8 @@ void Model::backward_G_streamed(float label_real) {
 
 // BaseGAN.optimize_parameters as a recorded launch sequence (engine.h Model::step_captured)
 void Model::step_captured(const float labels[3], bool training, uint64_t seed) {
-  static_assert(sizeof(StepParams) == 40 && offsetof(StepParams, schedG) == 24 && offsetof(StepParams, schedD) == 32, "StepParams layout");
+  static_assert(sizeof(StepParams) == 64 && offsetof(StepParams, schedG) == 24 && offsetof(StepParams, schedD) == 32 &&
+                offsetof(StepParams, boundG) == 40 && offsetof(StepParams, boundD) == 52, "StepParams layout (64 bytes allocated)");
   if (hyper.gp_mode) { step(labels, training, seed); return; }          // host-seeded draws per step: not recordable
   if (!sp_dev) { AllocScope mine(*ctx, owned_allocs); sp_dev = static_cast<StepParams*>(ctx->alloc(64)); }
   StepParams h{};
@@ -1539,6 +1553,10 @@ void Model::step_captured(const float labels[3], bool training, uint64_t seed) {
   h.seed = seed;
   adamw_schedule(hyper.lr, hyper.b1, hyper.b2, arenaG.step + 1, h.schedG);
   adamw_schedule(hyper.d_lr, hyper.d_b1, hyper.d_b2, arenaD.step + 1, h.schedD);
+  if (arenaG.opt_kind == OPT_ADABOUND)
+    adabound_schedule(hyper.lr, hyper.b1, hyper.b2, arenaG.final_lr, arenaG.base_lr, arenaG.gamma, arenaG.step + 1, h.boundG);
+  if (arenaD.opt_kind == OPT_ADABOUND)
+    adabound_schedule(hyper.d_lr, hyper.d_b1, hyper.d_b2, arenaD.final_lr, arenaD.base_lr, arenaD.gamma, arenaD.step + 1, h.boundD);
   dev_store_small(ctx->s, sp_dev, &h, sizeof h);      // stream-ordered, in front of this step's launches, and NO host sync (round 5: the
                                                       // synchronising upload made every replayed step wait for the previous one to drain)
   struct Indirect {
@@ -1553,7 +1571,8 @@ void Model::step_captured(const float labels[3], bool training, uint64_t seed) {
     return;
   }
   // a recorded sequence bakes in what is not in StepParams: one stream or two, and where AdamW sits (round-4 advice)
-  const int key = (ctx->use_side() ? 1 : 0) | (env_int(getenv("SWN_STREAM_ADAMW"), 1) << 1);
+  // ... and which update kernel each network's optimizer launches (the arenas, and so the kinds, may be shared with other models)
+  const int key = (ctx->use_side() ? 1 : 0) | (env_int(getenv("SWN_STREAM_ADAMW"), 1) << 1) | (arenaG.opt_kind << 8) | (arenaD.opt_kind << 12);
   if (step_graph_[gi] && step_graph_key_[gi] != key) { graph_destroy(step_graph_[gi]); step_graph_[gi] = nullptr; }
   if (!step_graph_[gi]) {
     step_graph_key_[gi] = key;

@@ -111,6 +111,10 @@ struct ParamArena {
   size_t n = 0;
   float *w = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
   int step = 0;
+  // the update optimizer_step applies to this arena (ops.h OptKind) and AdaBound's own parameters; next to the step counter
+  // because models that share the arena share the optimizer
+  int opt_kind = 0;
+  float final_lr = 0.1f, base_lr = 0.f, gamma = 1e-3f;
   int version = 1;        // bumped whenever the weights change (dgrad operands follow it)
   bool frozen = false;    // after allocate(): builders may only re-bind existing params (shared nets)
   int add_weight(const std::string& name, int kind, int Co, int Ci, int KH, int KW, int Cip,
@@ -397,6 +401,9 @@ class Model {
   int backward_G_parts() const;
   void backward_G_part(float label_real, int part, size_t* ready_off, size_t* ready_count, bool join = true);
   void optimizer_step(int net);
+  // everything adamw_step needs for `net` except the range: hyper-parameters, the arena's optimizer kind, and (captured step) where
+  // this step's schedule lies in sp_dev.  Throws when the arena asks for an update this build does not have.
+  AdamWArgs optimizer_args(int net);
   // AdamW on the arena range [off, off + count) only (data parallel: a bucket is stepped as soon as its all-reduce
   // has landed, under the back-propagation of the next bucket).  first != 0 opens a new optimizer step (advances
   // the bias-correction counter); the ranges of one step must tile the arena.
@@ -416,14 +423,14 @@ class Model {
   // collectives are identities and the result equals step()'s.
   void step_dp(const float labels[3], bool training, uint64_t seed, bool after_forward);
   // The same step recorded ONCE into a hipGraph (per value of `training`) and replayed: every per-step scalar -- the three
-  // smooth labels (modules/loss.py:77-104), the dropout seed, the bias corrections of both AdamW steps -- lives in a small
+  // smooth labels (modules/loss.py:77-104), the dropout seed, the bias corrections of both AdamW steps (AdaBound: step size and both bounds) -- lives in a small
   // device block (StepParams) that is uploaded in stream order before each launch, so the recorded launch sequence (two
   // streams, ~620 kernels) is identical for every step.  train.py:74's loss read-back stays the only synchronisation.
   // First call per mode runs eagerly (kernel attributes, lazy buffers), the second records, later ones replay.  Not for the
   // gradient-penalty modes (their alpha / beta draws are host-seeded per step) nor under data parallelism (the exchange
   // runs through torch.distributed between the phases): those keep step().  Results are bit-identical to step().
   void step_captured(const float labels[3], bool training, uint64_t seed);
-  struct StepParams { float labels[4]; uint64_t seed; float schedG[2]; float schedD[2]; };
+  struct StepParams { float labels[4]; uint64_t seed; float schedG[2]; float schedD[2]; float boundG[3]; float boundD[3]; };
   StepParams* sp_dev = nullptr;
   bool indirect = false;          // the phases read labels / seed / AdamW schedule from sp_dev
   const float* label_dev(int i) const { return indirect ? reinterpret_cast<const float*>(sp_dev) + i : nullptr; }

@@ -6,6 +6,7 @@
 // never part of the shipped library.
 #pragma once
 #include "common.h"
+#include <cmath>
 
 namespace swn {
 
@@ -389,9 +390,25 @@ struct AdamWArgs {
   // optional (captured training step): {lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step)} of THIS step in device memory, as
   // adamw_schedule computes them; `step` is then ignored
   const float* sched_dev = nullptr;
+  // which update adamw_step applies: 0 = AdamW, 1 = AdaBound (Luo et al., ICLR 2019, as adabound 0.0.5 runs it with amsbound off;
+  // reference optimizers/__init__.py:37-60).  AdaBound: weight_decay is the COUPLED L2 term (g += wd * p), the per-element rate
+  // step_size / (sqrt(v) + eps) is clamped to [lower, upper] of adabound_schedule, and sched_dev holds that schedule's three values.
+  int kind = 0;
+  float final_lr = 0.1f, base_lr = 0.f, gamma = 1e-3f;   // AdaBound only; base_lr = the lr the optimizer was constructed with
 };
+enum OptKind : int { OPT_ADAMW = 0, OPT_ADABOUND = 1 };
 void adamw_step(Stream& s, const AdamWArgs& a);
 void adamw_schedule(float lr, float beta1, float beta2, int step, float out[2]);
+// AdaBound's per-step scalars {step_size, lower, upper}, in double like adamw_schedule.  Defined here (not in a backend's
+// translation unit) because the engine fills StepParams with it and every backend links the engine.
+inline void adabound_schedule(float lr, float beta1, float beta2, float final_lr, float base_lr, float gamma, int step, float out[3]) {
+  const double bc1 = 1.0 - std::pow((double)beta1, step);
+  const double bc2 = 1.0 - std::pow((double)beta2, step);
+  const double fin = (double)final_lr * (double)lr / (double)base_lr;
+  out[0] = (float)((double)lr * std::sqrt(bc2) / bc1);
+  out[1] = (float)(fin * (1.0 - 1.0 / ((double)gamma * step + 1.0)));
+  out[2] = (float)(fin * (1.0 + 1.0 / ((double)gamma * step)));
+}
 
 enum WKind : int { WK_CONV = 0, WK_CONVT = 1 };
 // Packed weight layouts (all [K][Npad], row-major):

@@ -1,6 +1,7 @@
-// swapnet_amd -- fused AdamW over a whole parameter arena + weight layout transforms.
+// swapnet_amd -- fused AdamW / AdaBound over a whole parameter arena + weight layout transforms.
 // Reference: optimizers/__init__.py:37-60 -> torch.optim.AdamW (decoupled weight decay,
-// eps 1e-8, amsgrad off); state-dict weight layouts of Conv2d (Co,Ci,KH,KW) and
+// eps 1e-8, amsgrad off) or adabound.AdaBound (coupled L2, gamma 1e-3, eps 1e-8, amsbound off; restated from
+// the published update, the package is not a dependency); state-dict weight layouts of Conv2d (Co,Ci,KH,KW) and
 // ConvTranspose2d (Ci,Co,4,4) (modules/layers.py:15,31).
 // AdamW is 28 B/param of HBM traffic (read p,g,m,v; write p,m,v) -> purely bandwidth bound:
 // one launch over the contiguous arena, 16-byte accesses, grid-stride.
@@ -28,6 +29,35 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamWArgs a, float decay, fl
       const float denom = sqrtf(vj) * inv_sqrt_bc2 + a.eps;
       pj -= step_size * (mj / denom);
       pp[j] = pj; mp[j] = mj; vp[j] = vj;
+    }
+    reinterpret_cast<float4*>(a.p)[i] = p;
+    reinterpret_cast<float4*>(a.m)[i] = m;
+    reinterpret_cast<float4*>(a.v)[i] = v;
+  }
+}
+
+// AdaBound: Adam's moments, no bias correction inside denom, the per-element rate clamped to bounds that close in on final_lr.
+// Same traffic as adamw_kernel (28 B/param), same launch shape.
+__global__ __launch_bounds__(256) void adabound_kernel(AdamWArgs a, float step_size, float lower, float upper) {
+  if (a.sched_dev) { step_size = a.sched_dev[0]; lower = a.sched_dev[1]; upper = a.sched_dev[2]; }      // captured step
+  const size_t n4 = a.n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    float4 p = reinterpret_cast<float4*>(a.p)[i];
+    const float4 g = reinterpret_cast<const float4*>(a.g)[i];
+    float4 m = reinterpret_cast<float4*>(a.m)[i];
+    float4 v = reinterpret_cast<float4*>(a.v)[i];
+    float* pp = &p.x; const float* gp = &g.x; float* mp = &m.x; float* vp = &v.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      // adabound 0.0.5 order: g += wd*p; m = b1*m + (1-b1)g; v = b2*v + (1-b2)g*g; denom = sqrt(v) + eps;
+      // p -= clamp(step_size / denom, lower, upper) * m.  g = 0, v = 0: step_size / eps clamps to upper, times m = 0.
+      const float gj = gp[j] + a.weight_decay * pp[j];
+      const float mj = mp[j] * a.beta1 + (1.f - a.beta1) * gj;
+      const float vj = vp[j] * a.beta2 + (1.f - a.beta2) * gj * gj;
+      const float denom = sqrtf(vj) + a.eps;
+      const float rate = fminf(fmaxf(step_size / denom, lower), upper);
+      pp[j] -= rate * mj;
+      mp[j] = mj; vp[j] = vj;
     }
     reinterpret_cast<float4*>(a.p)[i] = p;
     reinterpret_cast<float4*>(a.m)[i] = m;
@@ -199,12 +229,21 @@ void adamw_schedule(float lr, float beta1, float beta2, int step, float out[2]) 
 }
 void adamw_step(Stream& s, const AdamWArgs& a) {
   if (a.n % 4) throw Error(1, "adamw_step: arena size must be a multiple of 4");
+  const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>((a.n / 4 + 255) / 256, 1), 256 * 16);
+  if (a.kind == OPT_ADABOUND) {
+    if (!(a.base_lr > 0.f) || !(a.gamma > 0.f)) throw Error(1, "adamw_step: AdaBound needs base_lr > 0 and gamma > 0");
+    float b[3];
+    adabound_schedule(a.lr, a.beta1, a.beta2, a.final_lr, a.base_lr, a.gamma, a.step, b);
+    hipLaunchKernelGGL(adabound_kernel, dim3(grid), dim3(256), 0, hs(s), a, b[0], b[1], b[2]);
+    check_launch("adamw_step(adabound)");
+    return;
+  }
+  if (a.kind != OPT_ADAMW) throw Error(1, "adamw_step: unknown optimizer kind");
   float sched[2];
   adamw_schedule(a.lr, a.beta1, a.beta2, a.step, sched);
   const float decay = 1.f - a.lr * a.weight_decay;
   const float step_size = sched[0];
   const float inv_sqrt_bc2 = sched[1];
-  const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>((a.n / 4 + 255) / 256, 1), 256 * 16);
   hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, hs(s), a, decay, step_size, inv_sqrt_bc2);
   check_launch("adamw_step");
 }

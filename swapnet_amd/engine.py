@@ -13,6 +13,7 @@ import torch
 from . import _C
 
 NET_G, NET_D, NET_VGG = 0, 1, 2
+OPT_ADAMW, OPT_ADABOUND = 0, 1
 W_WEIGHT, W_GRAD, W_EXP_AVG, W_EXP_AVG_SQ = 0, 1, 2, 3
 
 
@@ -39,6 +40,8 @@ class Context:
         h = C.c_void_p()
         self.lib.call("swn_ctx_create", dev_index, stream, create, C.c_size_t(workspace_mb << 20), C.byref(h))
         self.handle = h
+        # the library's main stream is its own non-blocking one: nothing orders it with torch's streams (see NativeModel._torch_done)
+        self.owns_stream = bool(create)
         self._copy_stream = None
 
     def upload(self, tensor, dtype, key=None):
@@ -199,6 +202,7 @@ class NativeModel:
 
     def set_param(self, net, name, tensor, which=W_WEIGHT):
         t = self._dev(tensor)
+        self._torch_done()
         self.lib.call("swn_model_param_set", self.handle, net, which, name.encode(), _C.ptr(t))
         self._sync_if_needed()
 
@@ -210,8 +214,17 @@ class NativeModel:
 
     def _sync_if_needed(self):
         # the library runs on torch's current stream, so torch frees/reuses are ordered; a
-        # private stream would need an explicit sync before temporaries die
-        pass
+        # private stream needs an explicit sync before the temporaries die or torch reads what the library wrote
+        if self.ctx.owns_stream:
+            self.ctx.sync()
+
+    def _torch_done(self):
+        """Before the library reads a tensor torch just produced (an upload, a conversion): on torch's current stream the call is
+        ordered behind it for free; a context that owns its stream (hipStreamNonBlocking, not even ordered with the null stream)
+        has to wait for torch.  Without this, the pack kernel of one parameter could still be reading the temporary that torch's
+        allocator had already handed to the next parameter's upload."""
+        if self.ctx.owns_stream:
+            torch.cuda.current_stream(self.ctx.device).synchronize()
 
     def load_state_dict(self, net, sd, which=W_WEIGHT, strict=True):
         infos = self.param_infos(net)
@@ -250,6 +263,11 @@ class NativeModel:
             setattr(h, k, v)
         self.lib.call("swn_model_set_hyper", self.handle, C.byref(h))
 
+    def set_optimizer(self, net, kind=OPT_ADAMW, final_lr=0.1, base_lr=0.0, gamma=1e-3):
+        """The update optimizer_step / step apply to `net` (swn_model_set_optimizer): OPT_ADAMW or OPT_ADABOUND with its
+        final_lr, base_lr (the lr it was constructed with) and gamma; lr, betas and weight decay stay in set_hyper."""
+        self.lib.call("swn_model_set_optimizer", self.handle, net, int(kind), C.c_float(final_lr), C.c_float(base_lr), C.c_float(gamma))
+
     # ---- data / step ----------------------------------------------------------------------
     def set_input(self, slot, tensor):
         t, token = self.ctx.upload(tensor, torch.float32, key=(id(self), "in", slot))
@@ -257,7 +275,9 @@ class NativeModel:
             n, c, h, w = t.shape[0], t.shape[1], t.shape[2], 1
         else:
             n, c, h, w = t.shape
+        self._torch_done()
         self.lib.call("swn_model_set_input", self.handle, slot, _C.ptr(t), n, c, h, w)
+        self._sync_if_needed()
         self.ctx.consumed(token)
         self._keep = [t]
 
@@ -265,7 +285,9 @@ class NativeModel:
         """Integer cloth label map (B,H,W) -> one-hot expansion on the device."""
         t, token = self.ctx.upload(labels, torch.int32, key=(id(self), "lab", slot))
         n, h, w = t.shape
+        self._torch_done()
         self.lib.call("swn_model_set_input_labels", self.handle, slot, _C.ptr(t), n, h, w)
+        self._sync_if_needed()
         self.ctx.consumed(token)
         self._keep_labels = t
 
@@ -308,6 +330,7 @@ class NativeModel:
         """Global (all ranks') generated / target images for the style term of the next backward_G (data parallel)."""
         o = all_out.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
         t = all_tgt.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        self._torch_done()
         self.lib.call("swn_model_set_style_context", self.handle, _C.ptr(o), _C.ptr(t), int(o.shape[0]), int(n0))
         self._style_keep = (o, t)
 
@@ -315,6 +338,7 @@ class NativeModel:
         """alpha (B,) / (B,1,1,1) and beta (B,C_D,H,W): the gradient-penalty draws of the next backward_D (one-shot)."""
         a = None if alpha is None else alpha.detach().reshape(-1).to(device=self.ctx.device, dtype=torch.float32).contiguous()
         b = None if beta is None else beta.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        self._torch_done()
         self.lib.call("swn_model_set_gp_random", self.handle, _C.ptr(a), _C.ptr(b))
         self._gp_keep = (a, b)
 
@@ -328,6 +352,7 @@ class NativeModel:
         k = self.n_layers_D                     # n stride-2 levels, then two 4x4 stride-1 convs with padding 1 (-1 pixel each)
         shape = (self.B, 1, (self.H >> k) - 2, (self.W >> k) - 2) if k > 0 else (self.B, 1, self.H, self.W)     # 0: PixelDiscriminator
         pred = torch.empty(shape, dtype=torch.float32, device=self.ctx.device)
+        self._torch_done()
         self.lib.call("swn_model_discriminate", self.handle, _C.ptr(xd), _C.ptr(pred))
         self.ctx.sync()
         return pred
@@ -340,6 +365,7 @@ class NativeModel:
             raise ValueError("perceptual loss inputs must both be (%d, 3, %d, %d)" % (self.B, self.H, self.W))
         out2 = torch.empty(2, dtype=torch.float32, device=self.ctx.device)
         d = torch.empty_like(o) if want_grad else None
+        self._torch_done()
         self.lib.call("swn_model_perceptual", self.handle, _C.ptr(o), _C.ptr(t), int(bool(use_style)), _C.ptr(out2),
                       C.c_float(content_w), C.c_float(style_w), _C.ptr(d))
         self.ctx.sync()

@@ -26,6 +26,7 @@ class NativeBackend:
         self.models = {}
         self.cur = None
         self.hyper = {}
+        self.optim = {}             # net -> set_optimizer keywords (AdamW where absent)
         self.training = {engine.NET_G: True, engine.NET_D: True}
         self._pending = {}          # state dicts loaded before any shape is known
 
@@ -39,6 +40,8 @@ class NativeBackend:
                                    dropout=self.dropout, num_roi=self.num_roi, body_channels=self.body_channels,
                                    cloth_channels=self.cloth_channels, n_layers_D=self.n_layers_D, share=root)
             m.set_hyper(**self.hyper)
+            for net, kw in self.optim.items():
+                m.set_optimizer(net, **kw)
             self.models[key] = m
         if self.cur is None and self._pending:
             for (net, which), sd in list(self._pending.items()):
@@ -61,6 +64,11 @@ class NativeBackend:
         self.hyper.update(kw)
         for m in self.models.values():
             m.set_hyper(**self.hyper)
+
+    def set_optimizer(self, net, **kw):
+        self.optim[net] = kw
+        for m in self.models.values():      # the arenas are shared, the recorded step graphs are each model's own
+            m.set_optimizer(net, **kw)
 
     # -- parameters ---------------------------------------------------------------------------
     def param_shapes(self, net):

@@ -1,8 +1,9 @@
-"""optimizers of the reference (/root/reference/optimizers/__init__.py): option modifiers and
-`define_optimizer`, returning an object with the torch.optim.Optimizer surface the reference
-uses (zero_grad / step / state_dict / load_state_dict / param_groups) backed by the fused HIP
-AdamW over the network's flat arena.  AdaBound (non-default; its package is not even
-installable offline) is not implemented."""
+"""optimizers of the reference (optimizers/__init__.py): option modifiers and `define_optimizer`,
+returning an object with the torch.optim.Optimizer surface the reference uses (zero_grad / step /
+state_dict / load_state_dict / param_groups) backed by a fused HIP update over the network's flat
+arena: AdamW (default) or AdaBound, chosen per network by --optimizer_G / --optimizer_D.  AdaBound
+restates the published update (Luo et al., ICLR 2019) as adabound 0.0.5 executes it; the package
+itself is not a dependency and is never imported."""
 from argparse import ArgumentParser
 from collections import OrderedDict
 
@@ -90,17 +91,63 @@ class NativeAdamW:
         self.sync()
 
 
+class NativeAdaBound(NativeAdamW):
+    """adabound.AdaBound(lr, betas, final_lr, gamma=1e-3, eps=1e-8, weight_decay, amsbound=False) over one arena:
+    weight_decay is the coupled L2 term, and the bounds close in on final_lr * lr / base_lr, base_lr being the lr of
+    construction (the package's `base_lrs`, which is not part of its state dict either)."""
+
+    def __init__(self, backend, net, lr, weight_decay, betas, final_lr, gamma=1e-3):
+        if not backend.ctx.lib.is_device:
+            raise NotImplementedError("AdaBound is a HIP kernel only: the host simulator library has no AdaBound update")
+        self.backend, self.net = backend, net
+        self.base_lr = float(lr)
+        self.param_groups = [dict(lr=lr, betas=tuple(betas), final_lr=final_lr, gamma=gamma, eps=1e-8,
+                                  weight_decay=weight_decay, amsbound=False)]
+        self._pushed = self._pushed_bound = None
+        self.sync()
+
+    def sync(self):
+        """As NativeAdamW.sync, plus final_lr / gamma: edits take effect at the next step."""
+        super().sync()
+        g = self.param_groups[0]
+        if g.get("amsbound"):
+            raise NotImplementedError("AdaBound with amsbound=True is not implemented natively")
+        cur = (float(g["final_lr"]), float(g["gamma"]))
+        if cur != self._pushed_bound:
+            self.backend.set_optimizer(self.net, kind=engine.OPT_ADABOUND, final_lr=cur[0], base_lr=self.base_lr, gamma=cur[1])
+            self._pushed_bound = cur
+
+    def state_dict(self):
+        """adabound.AdaBound.state_dict() layout: state[i] = {step (int), exp_avg, exp_avg_sq}."""
+        sd = super().state_dict()
+        for st in sd["state"].values():
+            st["step"] = int(st["step"])
+        return sd
+
+    def load_state_dict(self, sd):
+        g = sd["param_groups"][0]
+        if "final_lr" not in g:
+            raise ValueError("not an AdaBound state dict: its param_groups carry no final_lr")
+        if g.get("amsbound", False):
+            raise NotImplementedError("AdaBound with amsbound=True is not implemented natively")
+        self.param_groups[0].update(final_lr=g["final_lr"], gamma=g.get("gamma", 1e-3))
+        super().load_state_dict(sd)
+
+
 def define_optimizer(parameters, opt, net: str):
     """optimizers.define_optimizer (:37-60).  `parameters` is the NativeNet (or its
     .parameters() generator is ignored): the optimizer binds to the net's backend."""
     if net != "D" and net != "G":
         raise ValueError(f"net arg must be 'D' or 'G', received {net}")
     choice = getattr(opt, "optimizer_" + net)
-    if choice != "AdamW":
-        raise NotImplementedError("optimizer %s is not implemented natively (AdamW only)" % choice)
+    if choice not in ("AdamW", "AdaBound"):
+        raise NotImplementedError("optimizer %s is not implemented natively (AdamW | AdaBound)" % choice)
     lr = opt.d_lr if net == "D" else opt.lr
     wd = opt.d_weight_decay if net == "D" else opt.weight_decay
     backend = getattr(parameters, "_backend", None)
     if backend is None:
         raise ValueError("define_optimizer expects the swapnet_amd network object (not .parameters())")
-    return NativeAdamW(backend, engine.NET_D if net == "D" else engine.NET_G, lr, wd, (opt.b1, opt.b2))
+    which = engine.NET_D if net == "D" else engine.NET_G
+    if choice == "AdaBound":
+        return NativeAdaBound(backend, which, lr, wd, (opt.b1, opt.b2), opt.final_lr)
+    return NativeAdamW(backend, which, lr, wd, (opt.b1, opt.b2))
