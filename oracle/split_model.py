@@ -1,7 +1,7 @@
 """numpy model of how the ring GEMM kernels form fp32 products on the 16-bit matrix cores (TEST INFRASTRUCTURE, like the
 rest of oracle/: imported by tests/ only, never by the product).
 
-Restates swapnet_amd/csrc/conv_gemm.hip:
+Restates swapnet_amd/csrc/conv_gemm.h (the operand cuts) and conv_ring.hip (the kernels that use them):
   * scale_exp / PC_TOP_A / PC_TOP_B      -- the power-of-two operand scale from the operand's amax
   * split8h + conv_precut_kernel (PL 2)  -- x * 2^k = h + l, h = fp16 (A: truncated, B: nearest), l = fp16(x * 2^k - h) nearest
   * conv_fwd_pc_kernel<..., PL = 2>      -- a b ~ h_a h_b + h_a l_b + l_a h_b in fp32, scales removed as two exact factors
@@ -15,7 +15,7 @@ PC_TOP_A, PC_TOP_B = 12, 10
 
 
 def scale_exp(amax, top):
-    """k with amax * 2^k in [2^(top-1), 2^top); 0 for a zero / non-finite operand; clamped to +-100 (conv_gemm.hip scale_exp)."""
+    """k with amax * 2^k in [2^(top-1), 2^top); 0 for a zero / non-finite operand; clamped to +-100 (conv_gemm.h scale_exp)."""
     amax = np.float32(amax)
     if not (amax > 0) or not np.isfinite(amax):
         return 0
@@ -68,7 +68,7 @@ def matmul_three_plane(a, b):
 
 def matmul_one_plane(a, b, ka=None, kb=None, truncate=False):
     """C = A @ B the way the one-plane configuration forms it (SWN_PC_PLANES=1 / SWN_WGRAD_PLANES=1, bench.py --precision f16:
-    conv_gemm.hip split8h1 and conv_precut_kernel with one plane): each operand ONE fp16 value of x * 2^k, rounded to nearest, one
+    conv_gemm.h split8h1 and conv_ring.hip conv_precut_kernel with one plane): each operand ONE fp16 value of x * 2^k, rounded to nearest, one
     MFMA per product, fp32 accumulation.  `truncate` cuts toward zero instead (what the test of the bias must reject).
 
     Error per output element.  u = 2^-11 is fp16's unit round-off.  A scaled element x' = x 2^k is either normal (|x'| >= 2^-14:

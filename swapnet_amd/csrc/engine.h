@@ -13,11 +13,6 @@
 
 namespace swn {
 
-// SWN_* switches, from the value getenv() returned: on unless set to 0 / an integer with a default.  The getenv("SWN_...")
-// itself stays at the call site: when it runs is part of each switch's contract (tests/test_route_switches.py)
-inline bool env_on(const char* v) { return !(v && atoi(v) == 0); }
-inline int env_int(const char* v, int dflt) { return v ? atoi(v) : dflt; }
-
 struct Ctx {
   Stream s;
   // Side stream for weight-gradient work (wgrad GEMMs, their Winograd transforms, bias gradients, slab

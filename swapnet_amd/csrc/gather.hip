@@ -296,8 +296,7 @@ void roi_align_fwd(Stream& s, const TView& tex, int C, const float* rois, int R,
   if (out.C < R * C || out.N != tex.N) throw Error(1, "roi_align_fwd: output view too small");
   const size_t total = (size_t)tex.N * out.H * out.W * R;
   // the wavefront-primitive form (roi_align_wave_kernel) wherever its layout conditions hold; SWN_ROI_WAVE=0 (read per launch): scalar
-  const char* e = getenv("SWN_ROI_WAVE");
-  if (!(e && atoi(e) == 0) && C <= 3 && tex.cs % 4 == 0 && tex.cs >= 4) {
+  if (env_on(getenv("SWN_ROI_WAVE")) && C <= 3 && tex.cs % 4 == 0 && tex.cs >= 4) {
     const size_t nwork = (size_t)tex.N * out.H * ((out.W + 63) / 64);
     hipLaunchKernelGGL(roi_align_wave_kernel, dim3((unsigned)std::min<size_t>((nwork + 3) / 4, 256 * 32)), dim3(256), 0, hs(s), tex.p, tex.cs,
                        tex.H, tex.W, C, rois, tex.N, R, out.p, out.cs, out.H, out.W);

@@ -596,7 +596,7 @@ void norm_act_fwd(Stream& s, const NormActArgs& a) {
   p.norm = a.norm; p.act = a.act; p.drop_p = a.drop_p; p.seed = a.seed;
   p.amax_out = a.amax_out; p.seed_base = a.seed_base; p.salt = a.salt;
   if (a.norm && !a.stats) throw Error(1, "norm_act_fwd: stats buffer required");
-  p.pair_xcd = (p.C % 256 == 0 && !(getenv("SWN_IN_PAIR_XCD") && atoi(getenv("SWN_IN_PAIR_XCD")) == 0)) ? 1 : 0;
+  p.pair_xcd = (p.C % 256 == 0 && env_on(getenv("SWN_IN_PAIR_XCD"))) ? 1 : 0;
   if (a.norm && !a.partial_in && p.HW <= 1024 && p.C % 32 == 0 && fused_in_on()) {
     const dim3 grid(p.C / 32, p.N);
     // (above 512 pixels: 16-channel slabs of 64 KB, so several blocks share a CU and one block's load phase runs under
@@ -636,7 +636,7 @@ void norm_act_bwd(Stream& s, const NormActBwdArgs& a) {
   p.colsum = a.colsum;
   p.amax_out = a.amax_out; p.seed_base = a.seed_base; p.salt = a.salt;
   if (a.colsum && !(a.norm && norm_act_bwd_emits_colsum(p.HW, p.C))) throw Error(1, "norm_act_bwd: colsum requested on the chunked path");
-  p.pair_xcd = (p.C % 256 == 0 && !(getenv("SWN_IN_PAIR_XCD") && atoi(getenv("SWN_IN_PAIR_XCD")) == 0)) ? 1 : 0;
+  p.pair_xcd = (p.C % 256 == 0 && env_on(getenv("SWN_IN_PAIR_XCD"))) ? 1 : 0;
   if (a.norm && p.HW <= 1024 && p.C % 32 == 0 && fused_in_on()) {
     if (p.HW <= 64) hipLaunchKernelGGL((in_fused_bwd_kernel<32, 2>), dim3(p.C / 32, p.N), dim3(256), 0, hs(s), p);
     else if (p.HW <= 256) hipLaunchKernelGGL((in_fused_bwd_kernel<32, 8>), dim3(p.C / 32, p.N), dim3(256), 0, hs(s), p);

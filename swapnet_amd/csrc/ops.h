@@ -1,16 +1,22 @@
 // swapnet_amd -- device op launchers.  The engine (engine.cpp) is written against this
 // header only.  The product implementation is the set of HIP translation units in this
-// directory (conv_gemm.hip, norm_act.hip, losses.hip, optim.hip, gather.hip).
+// directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, losses.hip, optim.hip, gather.hip).
 // tests/hostsim/hostsim_ops.cpp implements the same signatures with plain loops so that
 // the engine's graph / backward / packing logic can be checked in CI without a GPU; it is
 // never part of the shipped library.
 #pragma once
 #include "common.h"
 #include <cmath>
+#include <cstdlib>
 
 namespace swn {
 
 struct WShape;
+
+// SWN_* switches, from the value getenv() returned: on unless set to 0 / an integer with a default.  The getenv("SWN_...")
+// itself stays at the call site: when it runs is part of each switch's contract (tests/test_route_switches.py)
+inline bool env_on(const char* v) { return !(v && atoi(v) == 0); }
+inline int env_int(const char* v, int dflt) { return v ? atoi(v) : dflt; }
 
 struct Stream {
   void* handle = nullptr;   // hipStream_t
@@ -57,7 +63,7 @@ void prof_enable(int on);
 void prof_reset();
 // one line per kernel variant: "<name> <launches> <total_ms> <total_flops>\n"; returns bytes written
 int prof_report(char* buf, int len);
-// swapnet_hip.h swn_probe_mfma: register-only fp16 MFMA loop, in-kernel clock (conv_gemm.hip); synchronises the stream
+// swapnet_hip.h swn_probe_mfma: register-only fp16 MFMA loop, in-kernel clock (prof.hip); synchronises the stream
 void probe_mfma(Stream& s, int zeros, int iters, float* out4);
 // Routing trace (swn_route_trace / swn_route_report, engine.cpp): which kernel family / algorithmic form every layer of a model
 // takes under the current environment.  While on, the engine labels each tape op as it runs it (phase f = forward, b = backward,
@@ -125,7 +131,7 @@ constexpr int AMAX_SLOT = 256;
 // produced (network inputs)
 void tensor_amax(Stream& s, const TView& x, float* slot, float floor = 0.f);
 void conv_fwd(Stream& s, const ConvFwdArgs& a);
-// Pre-cut weight operand of the LDS-DMA ring kernel (conv_gemm.hip conv_fwd_pc_kernel): x = hi + mid + lo, three bf16 planes by
+// Pre-cut weight operand of the LDS-DMA ring kernel (conv_ring.hip conv_fwd_pc_kernel): x = hi + mid + lo, three bf16 planes by
 // truncation (exact), laid out in MFMA operand order per 16-k stage and column tile.  conv_precut_tile: the column tile (64 /
 // 128) a forward-type launch over xC input channels into Npad columns takes, 0 = it would not use a pre-cut operand (host
 // simulator, narrow / first-layer launches, SWN_PRECUT=0): callers then need not produce one.
@@ -137,7 +143,7 @@ size_t conv_precut_elems(int K, int Npad, int bn);       // uint16 elements of o
 // stream scratch until the next pass) and for sources whose values are a subset of what the partials were taken over.
 void conv_precut(Stream& s, const float* w, int K, int Npad, int bn, int batch, size_t w_bs, uint16_t* out, const float** amax_io = nullptr);
 // Plane format of the pre-cut operands: 3 = three bf16 planes (six MFMAs per product), 2 = two fp16 planes of the operand times a
-// power of two chosen from its amax (three MFMAs; conv_gemm.hip "two fp16 planes").  In the two-plane form a panel carries a
+// power of two chosen from its amax (three MFMAs; conv_gemm.h "two fp16 planes").  In the two-plane form a panel carries a
 // 16-byte trailer with the scale exponent (counted by conv_precut_elems) and a producer first takes the 256 partial maxima of its
 // SOURCE tensor ([batch][rows][C] floats, dense rows, batch stride bs) with conv_precut_amax (NULL in the three-plane form).
 int conv_precut_planes();

@@ -10,7 +10,7 @@
 //
 // The element-wise products summed over input channels are P independent GEMMs
 // M[t] = V[t] (T x C) * U[t] (C x Co), executed by the MFMA implicit-GEMM kernel in batched mode
-// (conv_gemm.hip); this file holds the HBM-bound transforms around them:
+// (conv_gemm.hip and its kernel units); this file holds the HBM-bound transforms around them:
 //   wino_input_transform   d (input patches, reflect / zero padding) -> V[P][T][C]
 //   wino_filter_transform  packed W -> U[P][K][N]       (forward, or flipped+transposed for dgrad)
 //   wino_output_transform  M[P][T][Co] -> y (m x m per tile, ragged edge) + bias + activation
@@ -857,7 +857,7 @@ __global__ __launch_bounds__(256) void wino_s2_filter_grad_kernel(WShape w, int 
 }
 
 
-// ---- filter transform straight into the PRE-CUT operand layout of the ring kernel (conv_gemm.hip conv_fwd_pc_kernel) ----------
+// ---- filter transform straight into the PRE-CUT operand layout of the ring kernel (conv_ring.hip conv_fwd_pc_kernel) ----------
 // U[p][k][n] as above (mode 0: k = ci, n = co; mode 2: k = co, n = ci), but each thread produces the 8 consecutive k of one
 // (k / 8, column) entry, cuts them into the three bf16 planes and writes the 16-byte entries of
 //   out[p][stage = k / 16][tile_n][kq 2][plane 3][pos BN][8 k],  pos = (n % NB) * 32 + n / NB  (NB = BN / 32).
@@ -881,7 +881,7 @@ __device__ __forceinline__ void cut8_store(const float (&u)[8], wu32x4* o, size_
   o[e0 + 2 * plane_stride] = wu32x4{lo[0], lo[1], lo[2], lo[3]};
 }
 
-// two-plane fp16 form (conv_gemm.hip): u * 2^kB as h + l
+// two-plane fp16 form (conv_gemm.h): u * 2^kB as h + l
 typedef _Float16 wf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void cut8_store_h(const float (&u)[8], float sb, wu32x4* o, size_t e0, size_t plane_stride, bool low_plane) {
   unsigned hi[4], lo[4];
@@ -895,7 +895,7 @@ __device__ __forceinline__ void cut8_store_h(const float (&u)[8], float sb, wu32
   o[e0] = wu32x4{hi[0], hi[1], hi[2], hi[3]};
   if (low_plane) o[e0 + plane_stride] = wu32x4{lo[0], lo[1], lo[2], lo[3]};
 }
-__device__ __forceinline__ int wino_scale_exp(const float* part, int lane, int top) {      // as conv_gemm.hip scale_exp(amax256())
+__device__ __forceinline__ int wino_scale_exp(const float* part, int lane, int top) {      // as conv_gemm.h scale_exp(amax256())
   float m = fmaxf(fmaxf(part[lane], part[lane + 64]), fmaxf(part[lane + 128], part[lane + 192]));
 #pragma unroll
   for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));

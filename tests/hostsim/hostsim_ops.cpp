@@ -166,7 +166,7 @@ int conv_precut_planes() { return 2; }
 static bool sim_pair_on() { const char* e = getenv("SWN_SIM_PAIR"); return e && atoi(e) != 0; }
 // ---- the 16-bit operand formats of the device's ring kernels, as a rounding model (SWN_SIM_PAIR=1 only) ------------------------------
 // An operand element x enters the MFMAs as h + l, two fp16 values of x 2^k, k from the tensor's amax (top 2^12 for activations /
-// gradients, 2^10 for weights: conv_gemm.hip PC_TOP_A / PC_TOP_B).  Pre-cut weights and pair-form planes round h to nearest; an
+// gradients, 2^10 for weights: conv_gemm.h PC_TOP_A / PC_TOP_B).  Pre-cut weights and pair-form planes round h to nearest; an
 // activation cut in the loop truncates h (split8h), the weight gradient's dY operand rounds it (split8h_rn).  The simulator applies the
 // same cut to the fp32 value and multiplies the result -- what CPU CI then sees is the 22-bit operand arithmetic with the engine's
 // own choice of scales (slots, bounds, hand-overs), not the accumulation order of the MFMAs.
@@ -179,7 +179,7 @@ static float sim_f16_trunc(float x) {
   const int ue = std::max(e - 11, -24);
   return std::ldexp((float)std::trunc(std::ldexp((double)x, -ue)), ue);
 }
-static int sim_scale_exp(float amax, int top) {                 // as conv_gemm.hip scale_exp / wino.hip wino_scale_exp
+static int sim_scale_exp(float amax, int top) {                 // as conv_gemm.h scale_exp / wino.hip wino_scale_exp
   if (!(amax > 0.f) || amax > 3.0e38f) return 0;
   int e;
   std::frexp(amax, &e);                                          // amax = m 2^e, m in [0.5, 1): binary exponent e - 1

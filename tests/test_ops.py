@@ -316,7 +316,7 @@ def test_conv_wide_ring_tile(monkeypatch):
 @pytest.mark.gpu
 def test_split_main_loop_is_as_accurate_as_the_f32_mfma(monkeypatch):
     """The ring kernels form fp32 products on the 16-bit matrix pipe from two amax-scaled fp16 planes per operand (h h + h l + l h:
-    3 fp16 MFMA products, fp32 accumulate; conv_gemm.hip -- the three-plane bf16 form of rounds 2-3 left the library in round 5).
+    3 fp16 MFMA products, fp32 accumulate; conv_gemm.h / conv_ring.hip -- the three-plane bf16 form of rounds 2-3 left the library in round 5).
     Against a float64 convolution the result must be at least as close as the v_mfma_f32_32x32x2_f32 form (SWN_SPLIT=0) --
     forward, input gradient and weight gradient -- and the two forms must agree to fp32 round-off.  Inputs carry full 24-bit
     mantissas (randn)."""
@@ -347,7 +347,7 @@ def test_split_main_loop_is_as_accurate_as_the_f32_mfma(monkeypatch):
 def test_two_plane_form_on_heavy_tailed_operands(backend, monkeypatch):
     """The two-fp16-plane form scales an operand by ONE power of two per tensor, taken from its amax: an element keeps 22
     mantissa bits only while it lies within 2^-14 of the tensor's largest, below that the low plane runs into fp16's subnormal
-    range and the element's error becomes ABSOLUTE, amax * 2^-37 (conv_gemm.hip).  A single outlier 2^18 x the bulk -- gradient
+    range and the element's error becomes ABSOLUTE, amax * 2^-37 (conv_gemm.h).  A single outlier 2^18 x the bulk -- gradient
     tensors do this -- therefore costs every bulk element 4 bits.  This test pins that price at product level, element-wise
     and not only in rel-L2: forward (outlier in the activations), input gradient (outlier in dY) and weight gradient (outliers
     in both operands) against float64,

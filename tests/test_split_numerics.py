@@ -1,5 +1,5 @@
 """CPU pin of the arithmetic claim behind the ring kernels (no GPU): the numpy model in oracle/split_model.py restates the
-operand cuts of conv_gemm.hip; here its error against float64 is held to the figures DESIGN.md section 4 quotes from the
+operand cuts of conv_gemm.h; here its error against float64 is held to the figures DESIGN.md section 4 quotes from the
 GPU lab (profiles/ring_lab_r03_range.txt), including the failure modes the amax scale exists for."""
 import numpy as np
 import pytest
