@@ -39,7 +39,7 @@ typedef struct swn_ctx swn_ctx;
 typedef struct swn_model swn_model;
 
 int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lambda_gp; 4: swn_route_*, swn_model_step_captured, swn_model_create_shared;
-                                5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma */
+                                5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -89,6 +89,15 @@ int swn_probe_mfma(swn_ctx* ctx, int zeros, int iters, float* out4);
  * bench.py times) with the list of the run they check against the oracle. */
 int swn_route_trace(int on);
 int swn_route_report(char* buf, int len);
+/* Slot audit (diagnostic, no reference counterpart; off by default).  The GEMMs scale their fp16 operand planes by a power of two
+ * that usually comes from an "amax slot" the operand's producer filled, and the Winograd transforms cut their planes with a scale
+ * derived from such a slot and a gain bound.  While on, every launch that trusts a slot -- the convolution
+ * launches and the pair-form Winograd transforms -- also takes max |v| of exactly what it gathers, reads both back and fails
+ * (the call that issued the launch returns non-zero; swn_last_error names the launch, the slot value and the operand's amax) unless
+ * amax <= slot <= 4096 * amax; a pair-form transform additionally must leave |plane| * 2^k < 65504.  These are the conditions the CI
+ * simulator always checks on its own bookkeeping: there the call does nothing and succeeds.  Every audited launch synchronises, so
+ * a launch issued while a stream capture is open fails; swn_model_step_captured and swn_pipeline_run(use_graph) run unaudited. */
+int swn_slot_audit(int on);
 
 /* ---- models ---------------------------------------------------------------------------
  * swn_warp_model_create    <-> models.create_model(opt) with --model warp
@@ -304,6 +313,23 @@ int swn_op_labels_to_onehot(swn_ctx* ctx, const int32_t* labels, int b, int c, i
  * what: 0 forward, 1 weight gradient (y = dY in, w = dW out), 2 input gradient (y = dY in, x = dX out) */
 int swn_op_conv(swn_ctx* ctx, int kind, int transposed, int what, int naive, float* x, int n, int ci, int h, int w,
                 float* wgt, int co, const float* bias, int act, float* y);
+/* The same convolution with its operands PRODUCED on the tape, as inside a network: x0 -> [pre] -> x -> [conv] -> y -> [post] -> z.
+ * swn_op_conv fills x and dY from outside, so its launches take the amax of their operands themselves; here x and dY = y.g are
+ * written by kernels of the library, which leave the amax in the buffers' slots, and the conv launches take the producer-scaled
+ * routes a training step takes (pair-form Winograd planes, slot-scaled ring launches).
+ * pre:  0 identity, 1 InstanceNorm + LeakyReLU(0.2), 2 ReLU, 3 nearest upsample x2 (h, w even), 4 MaxPool2d(2, 2);
+ * post: 0 identity, 1 InstanceNorm + LeakyReLU(0.2).
+ * n, ci, h, w describe the CONV input x; x0 is (n, ci, h0, w0) with h0 = h / 2 (pre 3), 2 h (pre 4), else h.
+ * what 0: x = x0 in, y = z out.  what 1: x = x0 in, y = dZ in, wgt = weights in (the forward pass in front of
+ * the backward one runs on them; zeros will do behind identity stages) and dW out.  what 2: y = dZ in, wgt in, x = dX out, the gradient
+ * with respect to the conv input x, (n, ci, h, w); x0 is zero.  With pre = post = 0 every result equals swn_op_conv's.
+ * Optional outputs (device pointers, NULL to skip): x_out = the produced x, NCHW (n, ci, h, w); dy_out = y.g, NCHW (backward
+ * calls); x_slot, y_slot, z_slot, dy_slot = the 256 floats of the amax slot of x, y, z, y.g (an error when that buffer has no
+ * complete slot on the layer's route: y has one only behind a fused LeakyReLU / ReLU); kscale_out = the layer's published
+ * pair-form scale exponents, at most 8 ints in the order the layer reserved them (entries past its count are left untouched). */
+int swn_op_conv_produced(swn_ctx* ctx, int kind, int transposed, int what, int naive, float* x, int n, int ci, int h, int w,
+                         float* wgt, int co, const float* bias, int act, float* y, int pre, int post, float* x_out, float* x_slot,
+                         float* y_slot, float* z_slot, float* dy_out, float* dy_slot, int* kscale_out);
 /* InstanceNorm(+act) forward / backward on NCHW tensors (modules/__init__.py:66-69) */
 int swn_op_instance_norm_act(swn_ctx* ctx, const float* x, int n, int c, int h, int w, int act, float* y);
 int swn_op_instance_norm_act_bwd(swn_ctx* ctx, const float* x, const float* dy, int n, int c, int h, int w, int act,

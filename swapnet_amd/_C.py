@@ -44,6 +44,7 @@ _PROTOS = {
     "swn_probe_mfma": ([_vp, _i, _i, C.POINTER(C.c_float)], _i),
     "swn_route_trace": ([_i], _i),
     "swn_route_report": ([C.c_char_p, _i], _i),
+    "swn_slot_audit": ([_i], _i),
     "swn_warp_model_create": ([_vp, _i, _i, _i, _i, _f, C.POINTER(_vp)], _i),
     "swn_texture_model_create": ([_vp, _i, _i, _i, _i, _i, C.POINTER(_vp)], _i),
     "swn_warp_model_create_ex": ([_vp, _i, _i, _i, _i, _f, _i, _i, C.POINTER(_vp)], _i),
@@ -96,6 +97,7 @@ _PROTOS = {
     "swn_op_argmax_labels": ([_vp, _fp, _i, _i, _i, _i, _vp], _i),
     "swn_op_labels_to_onehot": ([_vp, _vp, _i, _i, _i, _i, _fp], _i),
     "swn_op_conv": ([_vp, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _fp, _i, _fp], _i),
+    "swn_op_conv_produced": ([_vp, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp], _i),
     "swn_op_instance_norm_act": ([_vp, _fp, _i, _i, _i, _i, _i, _fp], _i),
     "swn_op_instance_norm_act_bwd": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _fp], _i),
     "swn_op_affine_gather": ([_vp, _fp, _fp, _i, _i, _i, _i, _vp, _i], _i),

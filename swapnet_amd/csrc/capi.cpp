@@ -1,4 +1,5 @@
 // swapnet_amd -- extern "C" boundary (include/swapnet_hip.h).  Plain pointers and sizes only.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -57,7 +58,7 @@ static int guard(F f) {
 
 extern "C" {
 
-int swn_abi_version(void) { return 6; }
+int swn_abi_version(void) { return 7; }
 const char* swn_last_error(void) { return g_err.c_str(); }
 int swn_is_device_build(void) { return is_device_build(); }
 
@@ -124,6 +125,13 @@ int swn_probe_mfma(swn_ctx* ctx, int zeros, int iters, float* out4) {
 }
 int swn_route_trace(int on) { return guard([&] { route_enable(on); }); }
 int swn_route_report(char* buf, int len) { return route_report(buf, len); }
+int swn_slot_audit(int on) { return guard([&] { slot_audit(on); }); }
+// recorded launch sequences are never audited (the audit reads back): off for the duration of the call
+struct AuditSuspend {
+  int was = slot_audit_on();
+  AuditSuspend() { slot_audit(0); }
+  ~AuditSuspend() { slot_audit(was); }
+};
 
 int swn_warp_model_create_ex(swn_ctx* ctx, int batch, int height, int width, int is_train, float dropout,
                              int body_channels, int cloth_channels, swn_model** out) {
@@ -402,6 +410,7 @@ int swn_pipeline_run(swn_pipeline* p, int use_graph, int* graph_replayed) {
   return guard([&] {
     REQUIRE(p, "NULL argument");
     const bool had = p->p->graph_captured();
+    std::unique_ptr<AuditSuspend> unaudited(use_graph ? new AuditSuspend : nullptr);
     p->p->run(use_graph != 0);
     if (graph_replayed) *graph_replayed = (use_graph && had) ? 1 : 0;
   });
@@ -456,6 +465,7 @@ int swn_model_step_dp(swn_model* m, const float labels[3], int training, uint64_
 int swn_model_step_captured(swn_model* m, const float labels[3], int training, uint64_t seed) {
   return guard([&] {
     REQUIRE(m && labels && m->m->is_train, "model was not created for training");
+    AuditSuspend unaudited;
     m->m->step_captured(labels, training != 0, seed);
   });
 }
@@ -584,6 +594,86 @@ int swn_op_conv(swn_ctx* ctx, int kind, int transposed, int what, int naive, flo
         nhwc_to_nchw(s, xv.g, x, ci);
       }
     }
+    stream_sync(s);
+  });
+}
+
+int swn_op_conv_produced(swn_ctx* ctx, int kind, int transposed, int what, int naive, float* x, int n, int ci, int h, int w,
+                         float* wgt, int co, const float* bias, int act, float* y, int pre, int post, float* x_out, float* x_slot,
+                         float* y_slot, float* z_slot, float* dy_out, float* dy_slot, int* kscale_out) {
+  return guard([&] {
+    REQUIRE(ctx && x && wgt && y, "NULL argument");
+    REQUIRE(kind >= 0 && kind <= 5 && what >= 0 && what <= 2, "bad kind/what");
+    REQUIRE(what == 0 || act == ACT_NONE, "backward entry points take the gradient of the pre-activation output");
+    REQUIRE(pre >= 0 && pre <= 4 && post >= 0 && post <= 1, "bad pre/post stage");
+    REQUIRE(pre != 3 || (h % 2 == 0 && w % 2 == 0), "pre = upsample needs an even conv input");
+    REQUIRE(what != 0 || (!dy_out && !dy_slot), "dy_out / dy_slot belong to the backward calls");
+    struct Restore { ~Restore() { conv_force_naive(0); } } restore;
+    conv_force_naive(naive);
+    Ctx tmp(ctx->c->s);
+    ParamArena A;
+    Net net(tmp, A);
+    const int Cip = round_up(ci, 4), Cop = round_up(co, 4);
+    int Ho, Wo;
+    if (transposed) { Ho = 2 * h; Wo = 2 * w; }
+    else if (kind == CK_K4S2) { Ho = h / 2; Wo = w / 2; }
+    else if (kind == CK_K4S1) { Ho = h - 1; Wo = w - 1; }
+    else if (kind == CK_TAIL_UP) { Ho = 2 * h; Wo = 2 * w; }
+    else { Ho = h; Wo = w; }
+    // x0 -> [pre] -> x -> [conv] -> y -> [post] -> z: the conv's operands x and y.g are written by kernels of ours, on the tape
+    const int h0 = pre == 3 ? h / 2 : (pre == 4 ? 2 * h : h), w0 = pre == 3 ? w / 2 : (pre == 4 ? 2 * w : w);
+    Var x0 = net.alloc_var(n, h0, w0, Cip, false);
+    Var xv = net.alloc_var(n, h, w, Cip, true);
+    Var yv = net.alloc_var(n, Ho, Wo, Cop, true);
+    Var zv = net.alloc_var(n, Ho, Wo, Cop, true);
+    if (pre == 0) net.norm_act(x0, xv, false, ACT_NONE, 0.f);
+    else if (pre == 1) net.norm_act(x0, xv, true, ACT_LRELU, 0.f);
+    else if (pre == 2) net.act(x0, xv, ACT_RELU);
+    else if (pre == 3) net.upsample(x0, xv, 2);
+    else net.maxpool(x0, xv);
+    if (transposed) { REQUIRE(Cip == ci, "transposed conv needs Ci % 4 == 0"); net.convT("l", xv, yv, co, bias != nullptr); }
+    else net.conv("l", xv, yv, (ConvKind)kind, ci, co, bias != nullptr, act);
+    net.norm_act(yv, zv, post == 1, post == 1 ? ACT_LRELU : ACT_NONE, 0.f);
+    A.allocate(tmp);
+    net.finalize({});
+    Stream& s = tmp.s;
+    const ParamDesc& wd = A.params[A.index.at("l.weight")];
+    auto slot_of = [&](const float* base, const char* whose) -> const float* {
+      auto it = net.buf_slots.find(base);
+      if (it == net.buf_slots.end() || !it->second.complete || !net.amax) throw Error(1, std::string("swn_op_conv_produced: ") + whose + " has no complete amax slot on this route");
+      return net.amax + it->second.off;
+    };
+    auto copy_slot = [&](float* dst, const float* base, const char* whose) {
+      if (dst) dev_copy(s, dst, slot_of(base, whose), AMAX_SLOT * sizeof(float));
+    };
+    // (the backward calls run the forward pass too: it zeroes the slots and lets the producer of x fold)
+    if (what != 2) nchw_to_nhwc(s, x, n, ci, h0, w0, x0.v);
+    else dev_memset(s, x0.v.p, 0, x0.v.pixels() * x0.v.cs * sizeof(float));
+    pack_weight(s, wd.ws, wgt, A.w + wd.off);       // (what 1: the forward pass in front of the backward one runs on them)
+    if (bias) dev_copy(s, A.w + A.params[A.index.at("l.bias")].off, bias, co * sizeof(float));
+    net.forward();
+    if (x_out) nhwc_to_nchw(s, xv.v, x_out, ci);
+    copy_slot(x_slot, xv.vbase, "x");
+    copy_slot(y_slot, yv.vbase, "y");
+    copy_slot(z_slot, zv.vbase, "z");
+    if (what == 0) {
+      nhwc_to_nchw(s, zv.v, y, co);
+    } else {
+      nchw_to_nhwc(s, y, n, co, Ho, Wo, zv.g);
+      if (what == 1) {
+        net.refresh_dgrad();
+        net.backward(true, false);
+        unpack_weight(s, wd.ws, A.g + wd.off, wgt);
+      } else {
+        A.version += 1;
+        net.refresh_dgrad();
+        net.backward(false, true);
+        nhwc_to_nchw(s, xv.g, x, ci);
+      }
+      if (dy_out) nhwc_to_nchw(s, yv.g, dy_out, co);
+      copy_slot(dy_slot, yv.gbase, "y.g");
+    }
+    if (kscale_out && net.kscale_n) dev_copy(s, kscale_out, net.kscale, std::min<size_t>(net.kscale_n, 8) * sizeof(int));
     stream_sync(s);
   });
 }

@@ -930,6 +930,69 @@ void tensor_amax(Stream& s, const TView& x, float* slot, float floor) {
   amax_partials(s, x.p, x.pixels(), x.C, (size_t)x.cs, 1, 0, slot, 0, floor);
 }
 
+// ---- slot audit (hip_util.h) ------------------------------------------------------------------------------------------------
+static void audit_needs_sync(Stream& s, const char* launch) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  SWN_HIP_CHECK(hipStreamIsCapturing(hs(s), &st));
+  if (st != hipStreamCaptureStatusNone)
+    throw Error(1, std::string("slot audit: ") + launch + " on a stream with an open capture (the audit reads back: switch it off, swn_slot_audit(0))");
+}
+static float audit_slot_max(Stream& s, const float* slot) {
+  float h[AMAX_SLOT];
+  dev_download(s, h, slot, sizeof h);
+  float m = 0.f;
+  for (float v : h) m = (v > m || v != v) ? v : m;       // (a NaN entry makes the maximum NaN, as the consumers read it)
+  return m;
+}
+void audit_slot(Stream& s, const char* launch, const float* slot, const float* x, size_t rows, int C, size_t rs, int batch, size_t bs) {
+  audit_needs_sync(s, launch);
+  float* part = static_cast<float*>(dev_alloc(AMAX_SLOT * sizeof(float)));
+  float sv = 0.f, am = 0.f;
+  try {
+    amax_partials(s, x, rows, C, rs, batch, bs, part);
+    am = audit_slot_max(s, part);
+    sv = audit_slot_max(s, slot);
+  } catch (...) { dev_free(part); throw; }
+  dev_free(part);
+  char msg[256];
+  if (!(sv >= am) || (am > 0.f && !(sv <= 4096.f * am))) {
+    snprintf(msg, sizeof msg, "slot audit: %s: slot %.9g, operand amax %.9g (need amax <= slot <= 4096 * amax)", launch, (double)sv, (double)am);
+    throw Error(1, msg);
+  }
+}
+// max |h + l| over pair words {h | l << 16} (wino.hip pair4): the planes as stored, i.e. already times 2^k; an infinite or NaN
+// half reads as +inf
+__global__ __launch_bounds__(256) void pair_plane_amax_kernel(const unsigned* w, size_t n, float* out) {
+  float am = 0.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const unsigned u = w[i];
+    const _Float16 h = __builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)), l = __builtin_bit_cast(_Float16, (unsigned short)(u >> 16));
+    float v = fabsf((float)h + (float)l);
+    if (v != v) v = __builtin_inff();
+    am = fmaxf(am, v);
+  }
+  amax_fold(am, out);
+}
+void audit_pair_planes(Stream& s, const char* launch, const float* planes, size_t elems, const int* kscale) {
+  audit_needs_sync(s, launch);
+  float* part = static_cast<float*>(dev_alloc(AMAX_SLOT * sizeof(float)));      // (zero-filled)
+  float pm = 0.f;
+  int k = 0;
+  try {
+    const unsigned grid = (unsigned)std::min<size_t>((elems + 255) / 256, 1024);
+    hipLaunchKernelGGL(pair_plane_amax_kernel, dim3(grid ? grid : 1), dim3(256), 0, hs(s), reinterpret_cast<const unsigned*>(planes), elems, part);
+    check_launch("pair_plane_amax");
+    pm = audit_slot_max(s, part);
+    dev_download(s, &k, kscale, sizeof k);
+  } catch (...) { dev_free(part); throw; }
+  dev_free(part);
+  if (!(pm < 65504.f)) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "slot audit: %s: pair-form planes reach %.9g at the published scale 2^%d: past fp16's 65504", launch, (double)pm, k);
+    throw Error(1, msg);
+  }
+}
+
 // trailer of a ring launch whose tail round was split along K: the partial tiles summed in fixed order, then the epilogue
 template <int BM, int BN>
 static void reduce_ring_tail(Stream& s, const GemmP& p, const DmaSched& sc) {
@@ -985,6 +1048,8 @@ static void launch_fwd_pc_t(Stream& s, GemmP& p, int nb, const unsigned short* w
     // (the producer scaled and cut the operand: nothing to take the amax of)
   } else if (x_amax && amax_fused_on()) {
     a_amax = x_amax;          // the producer of the operand left its amax (256 floats, maximum = amax) in a slot: no pass of our own
+    if (slot_audit_on())
+      audit_slot(s, "conv_fwd", x_amax, p.x, (size_t)(p.M / (p.Ho * p.Wo)) * p.xH * p.xW, p.xC, (size_t)p.xcs, phases ? 1 : nb, p.x_bs);
   } else {
     // |A|max over the whole input tensor of the launch (all images, all channels the gather reads; batched planes too)
     float* part = ws_amax(s, 0);
@@ -1003,7 +1068,8 @@ static void launch_fwd_pc_t(Stream& s, GemmP& p, int nb, const unsigned short* w
   static bool once = (set_smem(conv_fwd_pc_kernel<WGM, NB, NSTG, WGCU, PL>, T::SMEM), true);
   (void)once;
   char pname[128];
-  prof_name(pname, "conv_fwd_pc_%dx%d", "%s[M%d,N%d,K%d,b%d,full%d,tail%dx%d]", T::BM, T::BN, x_pair_k ? "_ap" : "", p.M, p.Cout, p.K, nb,
+  // (_ap: the operand arrives in pair form, cut by its producer; _as: its scale comes from the producer's amax slot)
+  prof_name(pname, "conv_fwd_pc_%dx%d", "%s[M%d,N%d,K%d,b%d,full%d,tail%dx%d]", T::BM, T::BN, x_pair_k ? "_ap" : (a_amax == x_amax ? "_as" : ""), p.M, p.Cout, p.K, nb,
             sc.full, sc.tail_tiles, sc.tail_s);
   ProfScope prof(s, pname, 2.0 * p.M * p.Cout * p.K * nb);
   const int units = sc.full + sc.tail_tiles * sc.tail_s;
@@ -1081,10 +1147,16 @@ static void launch_wgrad_dma_t(Stream& s, GemmP& p, int nb, const ConvWgradArgs&
     const size_t nimg = (size_t)(p.M / (p.Ho * p.Wo));
     const bool fused = amax_fused_on();
     if (a.x_pair_k) xa = reinterpret_cast<const float*>(a.x_pair_k);
-    else if (a.x_amax && fused) xa = a.x_amax;
+    else if (a.x_amax && fused) {
+      xa = a.x_amax;
+      if (slot_audit_on()) audit_slot(s, "conv_wgrad (x)", a.x_amax, a.x.p, nimg * a.x.H * a.x.W, a.x.C, (size_t)a.x.cs, nbb, a.x_bs);
+    }
     else { float* px = ws_amax(s, 0); amax_partials(s, a.x.p, nimg * a.x.H * a.x.W, a.x.C, (size_t)a.x.cs, nbb, a.x_bs, px); xa = px; }
     if (a.dy_pair_k) ya = reinterpret_cast<const float*>(a.dy_pair_k);
-    else if (a.dy_amax && fused) ya = a.dy_amax;
+    else if (a.dy_amax && fused) {
+      ya = a.dy_amax;
+      if (slot_audit_on()) audit_slot(s, "conv_wgrad (dy)", a.dy_amax, a.dy.p, nimg * a.dy.H * a.dy.W, a.dy.C, (size_t)a.dy.cs, nbb, a.dy_bs);
+    }
     else { float* py = ws_amax(s, 1); amax_partials(s, a.dy.p, nimg * a.dy.H * a.dy.W, a.dy.C, (size_t)a.dy.cs, nbb, a.dy_bs, py); ya = py; }
   }
   const DmaSched sc = plan_dma(p.ntiles * nb, p.ntiles, nmb, 256 * wg_per_cu, (size_t)T::BMK * T::BN * 4, two ? s.ws_bytes - PC_WS_TAIL : s.ws_bytes);
@@ -1099,9 +1171,12 @@ static void launch_wgrad_dma_t(Stream& s, GemmP& p, int nb, const ConvWgradArgs&
                      p.yoff == 0 && p.xoff == 0 && p.M == p.Wo;
   const bool two_plane = two && wpl == 2 && plane;
   const int pairm = (a.x_pair_k ? 1 : 0) | (a.dy_pair_k ? 2 : 0);
+  // (_sx / _sy / _sxy behind the plane form: the scale of x / dy / both comes from the producer's amax slot, not from a pass of ours)
+  const int slotm = (two && xa && xa == a.x_amax ? 1 : 0) | (two && ya && ya == a.dy_amax ? 2 : 0);
   char pname[128];
-  prof_name(pname, "conv_wgrad_dma_%dx%d", "%s[M%d,N%d,K%d,b%d,full%d,tail%dx%d]", T::BMK, T::BN,
-            two ? (wpl == 1 ? "_h1" : (two_plane ? (pairm == 3 ? "_h2pp" : (pairm ? "_h2p1" : "_h2p")) : "_h2")) : "", p.M, p.Cout, p.K, nb,
+  prof_name(pname, "conv_wgrad_dma_%dx%d", "%s%s[M%d,N%d,K%d,b%d,full%d,tail%dx%d]", T::BMK, T::BN,
+            two ? (wpl == 1 ? "_h1" : (two_plane ? (pairm == 3 ? "_h2pp" : (pairm ? "_h2p1" : "_h2p")) : "_h2")) : "",
+            slotm == 3 ? "_sxy" : (slotm == 2 ? "_sy" : (slotm == 1 ? "_sx" : "")), p.M, p.Cout, p.K, nb,
             sc.full, sc.tail_tiles, sc.tail_s);
   ProfScope prof(s, pname, 2.0 * p.M * p.Cout * p.K * nb);
   const int units = sc.full + sc.tail_tiles * sc.tail_s;

@@ -31,6 +31,11 @@ void route_note(const char* kernel) {
   std::string line = g_route_label + " " + std::string(1, g_route_phase) + " " + kernel;
   if (g_route_seen.emplace(line, 1).second) g_route_lines.push_back(line);
 }
+// ---- slot audit (ops.h slot_audit) --------------------------------------------------------
+namespace { int g_slot_audit = 0; }
+void slot_audit(int on) { g_slot_audit = on; }
+bool slot_audit_on() { return g_slot_audit != 0; }
+
 int route_report(char* buf, int len) {
   std::string out;
   for (auto& l : g_route_lines) { out += l; out += "\n"; }

@@ -24,6 +24,14 @@ inline void check_launch(const char* what) {
   if (e != hipSuccess) throw Error(2, std::string("kernel launch failed (") + what + "): " + hipGetErrorString(e));
 }
 
+// ---- slot audit (ops.h slot_audit; conv_ring.hip) -- called by the launchers only while slot_audit_on() ----------------------
+// `slot` against the amax of the operand the launch gathers ([batch][rows][C] floats, row stride rs, batch stride bs): throws
+// unless amax <= max(slot) and, for amax > 0, max(slot) <= 4096 * amax (tests/hostsim/hostsim_ops.cpp sim_slot_check).  Synchronises.
+void audit_slot(Stream& s, const char* launch, const float* slot, const float* x, size_t rows, int C, size_t rs, int batch, size_t bs);
+// `elems` words a transform just wrote in pair form (a pair-form transform folds no amax of its planes: a pass over the words):
+// amax(plane) * 2^k, which is what the words hold, stays below 65504, the largest finite fp16.  Synchronises.
+void audit_pair_planes(Stream& s, const char* launch, const float* planes, size_t elems, const int* kscale);
+
 __device__ __forceinline__ float act_apply(float v, int act) {
   switch (act) {
     case ACT_LRELU: return v > 0.f ? v : 0.2f * v;

@@ -75,6 +75,14 @@ bool route_on();
 void route_label(const char* label, char phase);
 void route_note(const char* kernel);
 int route_report(char* buf, int len);      // returns the bytes the full report needs
+// Slot audit (swn_slot_audit, engine.cpp): the host simulator's sim_slot_check and pair-plane check, applied by the HIP launchers to
+// what the producers really left behind.  Off by default: one flag test per launch, like route_on().  While on, every launch that
+// takes an operand's scale from an amax slot (conv_fwd, conv_wgrad, the pair-form Winograd transforms) also takes the amax of exactly
+// what it gathers with a pass, reads both back and throws unless amax <= slot <= 4096 * amax; a pair-form transform additionally
+// requires amax(plane) * 2^k < 65504.  The read-back synchronises: an open stream capture is an error, step_captured is not audited.
+// The simulator always checks, so there the flag does nothing.
+void slot_audit(int on);
+bool slot_audit_on();
 
 // ---- implicit-GEMM convolution (MFMA) -----------------------------------------------
 // y[map(m)][co] (=|+=) act( sum_k A[m][k] * w[k][co] + bias[co] ),  A = gather(x)

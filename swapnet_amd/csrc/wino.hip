@@ -1200,6 +1200,10 @@ void wino_input_transform(Stream& s, int m, int r, const TView& x, int pad, int 
   else SWN_WIN_LAUNCH(F34, 2);
 #undef SWN_WIN_LAUNCH
   check_launch("wino_input_transform");
+  if (in_amax && slot_audit_on()) {
+    audit_slot(s, "wino_input_transform", in_amax, x.p, x.pixels(), x.C, (size_t)x.cs, 1, 0);
+    audit_pair_planes(s, "wino_input_transform", V, (size_t)(m + r - 1) * (m + r - 1) * x.N * Th * Tw * x.C, kscale_out);
+  }
 }
 void wino_filter_transform(Stream& s, int m, int r, const WShape& w, int mode, const float* packed, float* U) {
   const int v = variant(m, r);
@@ -1269,6 +1273,10 @@ void wino_dy_transform(Stream& s, int m, int r, const TView& dy, int Th, int Tw,
   else SWN_WDY_LAUNCH(F42, 2);
 #undef SWN_WDY_LAUNCH
   check_launch("wino_dy_transform");
+  if (in_amax && slot_audit_on()) {
+    audit_slot(s, "wino_dy_transform", in_amax, dy.p, dy.pixels(), dy.C, (size_t)dy.cs, 1, 0);
+    audit_pair_planes(s, "wino_dy_transform", dM, (size_t)(m + r - 1) * (m + r - 1) * dy.N * Th * Tw * dy.C, kscale_out);
+  }
 }
 void tailw_filter_transform(Stream& s, const WShape& w, const float* folded, float* U) {
   const size_t total = (size_t)w.Cip * 4 * w.Npad;
@@ -1293,6 +1301,10 @@ void tailw_dy_transform(Stream& s, const TView& dy, int Th, int Tw, int Npad, fl
   hipLaunchKernelGGL(tailw_dy_kernel, dim3(wgrid(total)), dim3(256), 0, hs(s), dy.p, dy.cs, dy.N, dy.H, dy.W, Th, Tw, Npad, dM, amax_out,
                      in_amax, 225.f, kscale_out);
   check_launch("tailw_dy_transform");
+  if (in_amax && slot_audit_on()) {
+    audit_slot(s, "tailw_dy_transform", in_amax, dy.p, dy.pixels(), dy.C, (size_t)dy.cs, 1, 0);
+    audit_pair_planes(s, "tailw_dy_transform", dM, (size_t)36 * dy.N * Th * Tw * 4 * Npad, kscale_out);
+  }
 }
 void wino_s2_input_transform(Stream& s, const TView& x, int Th, int Tw, float* V, float* amax_out, const float* in_amax, int* kscale_out) {
   if (x.C % 4 || x.cs % 4) throw Error(1, "wino_s2_input_transform: C must be a multiple of 4");
@@ -1301,6 +1313,10 @@ void wino_s2_input_transform(Stream& s, const TView& x, int Th, int Tw, float* V
   hipLaunchKernelGGL(wino_s2_input_kernel<2>, dim3(wgrid(total)), dim3(256), 0, hs(s), x.p, x.cs, x.N, x.H, x.W, x.C, Th, Tw, V,
                        amax_out, in_amax, 9.f, kscale_out);
   check_launch("wino_s2_input_transform");
+  if (in_amax && slot_audit_on()) {
+    audit_slot(s, "wino_s2_input_transform", in_amax, x.p, x.pixels(), x.C, (size_t)x.cs, 1, 0);
+    audit_pair_planes(s, "wino_s2_input_transform", V, (size_t)25 * x.N * Th * Tw * 4 * x.C, kscale_out);
+  }
 }
 void wino_s2_input_adjoint(Stream& s, float* dV, int Cf, int Th, int Tw, const TView& dx, const float* bias, int accumulate) {
   if (Cf % 4 || dx.C != Cf || dx.cs % 4) throw Error(1, "wino_s2_input_adjoint: bad channel count");

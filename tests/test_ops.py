@@ -49,7 +49,14 @@ def ref_conv(x, w, b, kind, transposed):
     return F.conv2d(up, w, b, padding=1)
 
 
-def run_conv(ctx, kind, transposed, what, naive, x, w, b, act, y_shape=None, dy=None):
+PRODUCED_OUTPUTS = ("x", "x_slot", "y_slot", "z_slot", "dy", "dy_slot", "kscale")       # optional outputs of swn_op_conv_produced, in argument order
+
+
+def run_conv(ctx, kind, transposed, what, naive, x, w, b, act, y_shape=None, dy=None, produced=None):
+    """produced = None: swn_op_conv (x and dY filled from outside the tape).  produced = a dict: swn_op_conv_produced, the same
+    convolution between a `pre` and a `post` stage (keys "pre", "post", default 0 = identity) so that its operands are written by
+    kernels of the library; x is then the input of the pre stage, dy the gradient of the post stage's output.  The optional
+    outputs named in produced["want"] (PRODUCED_OUTPUTS) come back in the dict as CPU tensors."""
     dev = ctx.device
     xd = x.to(dev).contiguous()
     wd = w.to(dev).contiguous()
@@ -60,9 +67,28 @@ def run_conv(ctx, kind, transposed, what, naive, x, w, b, act, y_shape=None, dy=
         yd = torch.empty(y_shape, device=dev)
     else:
         yd = dy.to(dev).contiguous()
-    ctx.lib.call("swn_op_conv", ctx.handle, kind, int(transposed), what, int(naive), _C.ptr(xd), n, ci, h, ww,
-                 _C.ptr(wd), co, _C.ptr(bd), act, _C.ptr(yd))
+    if produced is None:
+        ctx.lib.call("swn_op_conv", ctx.handle, kind, int(transposed), what, int(naive), _C.ptr(xd), n, ci, h, ww,
+                     _C.ptr(wd), co, _C.ptr(bd), act, _C.ptr(yd))
+        ctx.sync()
+        return {0: yd, 1: wd, 2: xd}[what].cpu()
+    pre, post = produced.get("pre", 0), produced.get("post", 0)
+    # n, ci, h, w of the call describe the CONV input: behind an upsampling pre stage it is twice x0, behind a max-pool half
+    h, ww = (2 * h, 2 * ww) if pre == 3 else ((h // 2, ww // 2) if pre == 4 else (h, ww))
+    if what == 2:
+        xd = torch.zeros((n, ci, h, ww), device=dev)          # dX out: the gradient with respect to the conv input
+    want = produced.get("want", ())
+    assert set(want) <= set(PRODUCED_OUTPUTS), want
+    shapes = {"x": ((n, ci, h, ww), torch.float32), "dy": (tuple(yd.shape), torch.float32), "kscale": ((8,), torch.int32)}
+    outs = {}
+    for k in want:
+        shape, dt = shapes.get(k, ((256,), torch.float32))
+        outs[k] = torch.full(shape, -(2 ** 30) if k == "kscale" else float("nan"), dtype=dt, device=dev)
+    ctx.lib.call("swn_op_conv_produced", ctx.handle, kind, int(transposed), what, int(naive), _C.ptr(xd), n, ci, h, ww,
+                 _C.ptr(wd), co, _C.ptr(bd), act, _C.ptr(yd), pre, post, *[_C.ptr(outs.get(k)) for k in PRODUCED_OUTPUTS])
     ctx.sync()
+    for k, v in outs.items():
+        produced[k] = v.cpu()
     return {0: yd, 1: wd, 2: xd}[what].cpu()
 
 
