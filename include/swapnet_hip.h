@@ -64,6 +64,21 @@ int swn_ctx_set_overlap(swn_ctx* ctx, int on);
  * pixel, state_dict keys net.{0,2,5}.{weight,bias}).  The gradient-penalty modes exist for every PatchGAN depth, not for the
  * PixelDiscriminator (swn_model_set_hyper fails). */
 int swn_ctx_set_patchgan_layers(swn_ctx* ctx, int n_layers);
+/* discriminators.define_D(..., norm) -> get_norm_layer(norm) (modules/discriminators.py:77, modules/__init__.py:53-74;
+ * models/base_gan.py:72-77,147-149): the norm layer of the discriminator of every WARP model created on this context
+ * AFTERWARDS.  0 = instance (default), 1 = batch (nn.BatchNorm2d, affine, running statistics), 2 = none (identity).
+ * Under 1 and 2 the convs in front of a norm layer carry no bias (use_bias is true only under InstanceNorm2d,
+ * modules/discriminators.py:104-107,151-154): the state dict has no model.{2,5,8}.bias / net.2.bias.  Under 1 every norm site
+ * adds model.K.weight / model.K.bias (K = 3, 6, ...; net.3 for the PixelDiscriminator) to the discriminator's parameters -- the
+ * optimizer, weight decay and the gradient exchange cover them like any parameter -- and the buffers model.K.running_mean /
+ * .running_var / .num_batches_tracked (swn_model_buffer_* below).  A training step updates the running statistics three
+ * times, as the reference's three discriminator calls do (models/warp_model.py:115-121,157-158): fake batch, real batch -- the
+ * two halves of the one 2B pass, normalised separately -- then the fakes through the updated discriminator.  Under data
+ * parallelism the statistics stay local to each rank (torch DDP's default).
+ * Not implemented (the library's "not implemented" error): texture models under kind != 0 (the flag also selects the norm layer
+ * of the texture stage's U-Net generator, modules/swapnet_modules.py:176-187, which exists under InstanceNorm only); the
+ * gradient-penalty modes under kind != 0; kind 1 on the CI simulator (HIP kernels only). */
+int swn_ctx_set_patchgan_norm(swn_ctx* ctx, int kind);
 int swn_ctx_sync(swn_ctx* ctx);
 int swn_ctx_bytes_allocated(swn_ctx* ctx, size_t* out);
 
@@ -229,6 +244,19 @@ int swn_model_set_gp_random(swn_model* m, const float* alpha_dev, const float* b
  * discriminator weights: x = conditioned input in the reference's channel order, (B, 22, H, W); pred receives
  * (B, 1, (H >> n) - 2, (W >> n) - 2), n = the PatchGAN depth (3: H/8-2).  Uses a private activation set: self.fakes and the staged batch stay untouched. */
 int swn_model_discriminate(swn_model* m, const float* x_nchw, float* pred_nchw);
+/* nn.Module.train(mode) of the discriminator for swn_model_discriminate (torch/nn/modules/module.py train / eval, as
+ * models/base_model.py:91-96 switches the reference's networks): training != 0 (the default, as a freshly built torch module) --
+ * BatchNorm sites normalise with the batch's statistics and update their running buffers, as torch would; 0 -- they normalise
+ * with the running buffers.  No effect under --norm instance / none.  The training step itself always runs in train mode. */
+int swn_model_set_discriminate_mode(swn_model* m, int training);
+/* state_dict() buffers of a network (torch.nn.BatchNorm2d's running_mean, running_var, num_batches_tracked under the keys of
+ * modules/discriminators.py:119,127,160: model.K.* / net.3.*): neither optimised nor exchanged.  Only the discriminator (net 1)
+ * under swn_ctx_set_patchgan_norm(ctx, 1) has any.  info: numel elements of fp32, or one int64 when *is_int64.  set / get copy
+ * between DEVICE pointers of that type.  Models sharing arenas (swn_model_create_shared) share the buffers. */
+int swn_model_buffer_count(swn_model* m, int net, int* out);
+int swn_model_buffer_info(swn_model* m, int net, int index, char* name, int name_len, int* numel, int* is_int64);
+int swn_model_buffer_set(swn_model* m, int net, const char* name, const void* src);
+int swn_model_buffer_get(swn_model* m, int net, const char* name, void* dst);
 /* PerceptualLoss(use_style)(output, target) -> (content, style) (modules/losses/perceptual.py:49-66), texture model:
  * output / target (B, 3, H, W); out2 = device float[2] = { sum over the 5 VGG16 slices of MSE(normalised features),
  * 5 x MSE(Gram(output), Gram(target)) }.  d_output (optional, (B,3,H,W)) receives content_w * d(content)/d(output)
@@ -334,6 +362,30 @@ int swn_op_conv_produced(swn_ctx* ctx, int kind, int transposed, int what, int n
 int swn_op_instance_norm_act(swn_ctx* ctx, const float* x, int n, int c, int h, int w, int act, float* y);
 int swn_op_instance_norm_act_bwd(swn_ctx* ctx, const float* x, const float* dy, int n, int c, int h, int w, int act,
                                  float* dx);
+/* BatchNorm2d(+act) forward / backward on NCHW tensors (modules/__init__.py:62-65: nn.BatchNorm2d(affine=True,
+ * track_running_stats=True), eps 1e-5, momentum 0.1; as used by modules/discriminators.py:118-120,126-128,159-161).
+ * groups (1 or 2): the batch is `groups` consecutive runs of n / groups images, and the call equals `groups` calls of the torch
+ * module on the runs in order -- each run normalised with its own biased statistics, the running buffers updated once per run with
+ * the unbiased variance, num_batches_tracked (device int64, optional) += groups.  This is how the discriminator's fake and real
+ * passes (models/warp_model.py:115-121) run as ONE 2B batch.  One value per channel and run (n / groups * h * w == 1) is refused
+ * as torch refuses it.  training = 0: normalise with the running buffers, which stay untouched (groups is ignored).
+ * weight, bias, running_mean, running_var: (c) device floats; the running buffers are updated IN PLACE (training; NULL = no
+ * update).  save_stats (optional, training): (groups, c, 2) = (mean, 1 / sqrt(var + eps)) of every run.
+ * _bwd: dy -> dx, dweight, dbias (both NULL: the parameter gradients are skipped, dx is the same) through the training-mode
+ * forward; with two groups the parameter gradients are the sum over the runs.
+ * HIP kernels only: the CI simulator returns the library's "not implemented" error. */
+int swn_op_batch_norm_act(swn_ctx* ctx, const float* x, int n, int c, int h, int w, int groups, int act, int training,
+                          const float* weight, const float* bias, float* running_mean, float* running_var,
+                          int64_t* num_batches_tracked, float* y, float* save_stats);
+int swn_op_batch_norm_act_bwd(swn_ctx* ctx, const float* x, const float* dy, int n, int c, int h, int w, int groups, int act,
+                              const float* weight, const float* bias, float* dx, float* dweight, float* dbias);
+/* The forward (what 0) or backward (what 1) pass of the layer behind swn_op_instance_norm_act (kind 0; modules/__init__.py:66-69) or
+ * swn_op_batch_norm_act (kind 1, training mode, weight 1, bias 0; modules/__init__.py:62-65) timed with HIP events on the
+ * context's stream: `warmup` untimed runs, then `iters` timed ones back to back on the same buffers, ms_out[i] (HOST floats) = the
+ * i-th.  Only the pass is timed -- no layout conversion, allocation or synchronisation inside the window (tools/bn_shapes.py).
+ * x, dy: (n, c, h, w) device tensors (dy only for what 1); groups: kind 1 only.  Device library only. */
+int swn_op_norm_act_time(swn_ctx* ctx, int kind, int what, const float* x, const float* dy, int n, int c, int h, int w, int groups,
+                         int act, int warmup, int iters, float* ms_out);
 /* WarpDataset's per-channel augmentation (datasets/warp_dataset.py:131-137, datasets/data_utils.py:346-361
  * per_channel_transform: an independent random flip / affine / perspective chain for each of the 19 cloth channels
  * of each sample) as ONE device gather over the batch instead of B*19*ntransforms PIL calls.  src, dst (B,C,H,W)

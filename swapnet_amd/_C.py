@@ -37,6 +37,7 @@ _PROTOS = {
     "swn_ctx_sync": ([_vp], _i),
     "swn_ctx_set_overlap": ([_vp, _i], _i),
     "swn_ctx_set_patchgan_layers": ([_vp, _i], _i),
+    "swn_ctx_set_patchgan_norm": ([_vp, _i], _i),
     "swn_ctx_bytes_allocated": ([_vp, C.POINTER(C.c_size_t)], _i),
     "swn_prof_enable": ([_i], _i),
     "swn_prof_reset": ([], _i),
@@ -75,6 +76,11 @@ _PROTOS = {
     "swn_model_set_style_context": ([_vp, _fp, _fp, _i, _i], _i),
     "swn_model_set_gp_random": ([_vp, _fp, _fp], _i),
     "swn_model_discriminate": ([_vp, _fp, _fp], _i),
+    "swn_model_set_discriminate_mode": ([_vp, _i], _i),
+    "swn_model_buffer_count": ([_vp, _i, C.POINTER(_i)], _i),
+    "swn_model_buffer_info": ([_vp, _i, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i)], _i),
+    "swn_model_buffer_set": ([_vp, _i, C.c_char_p, _vp], _i),
+    "swn_model_buffer_get": ([_vp, _i, C.c_char_p, _vp], _i),
     "swn_model_perceptual": ([_vp, _fp, _fp, _i, _fp, _f, _f, _fp], _i),
     "swn_model_forward": ([_vp, _i, C.c_uint64], _i),
     "swn_model_backward_D": ([_vp, _f, _f], _i),
@@ -100,6 +106,9 @@ _PROTOS = {
     "swn_op_conv_produced": ([_vp, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp], _i),
     "swn_op_instance_norm_act": ([_vp, _fp, _i, _i, _i, _i, _i, _fp], _i),
     "swn_op_instance_norm_act_bwd": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _fp], _i),
+    "swn_op_batch_norm_act": ([_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _vp, _fp, _fp], _i),
+    "swn_op_batch_norm_act_bwd": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp], _i),
+    "swn_op_norm_act_time": ([_vp, _i, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float)], _i),
     "swn_op_affine_gather": ([_vp, _fp, _fp, _i, _i, _i, _i, _vp, _i], _i),
     "swn_op_gan_loss": ([_vp, _i, _fp, _i, _i, _i, _i, _f, _i, _f, _fp, _fp], _i),
     "swn_op_norm_act_bwd2": ([_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp], _i),

@@ -1,0 +1,295 @@
+// swapnet_amd -- BatchNorm2d (eps 1e-5, momentum 0.1, affine, running statistics) + activation, forward and backward, on NHWC
+// views, with a GROUP dimension: the batch is `groups` consecutive runs of N / groups images and each run is normalised with its own
+// statistics and updates the running buffers on its own, in group order -- what the reference does when it calls the discriminator
+// once on the fakes and once on the targets, run here as one 2B batch.  Same split as norm_act.hip: per (image, pixel chunk, channel)
+// partial sums in fp64 -> a finalize kernel that reduces a group's partials in a fixed order -> one apply pass with 16-byte accesses.
+// No floating-point atomics: two runs on the same inputs are bit-identical.
+// Reference: modules/__init__.py:62-65 (BatchNorm2d(affine=True, track_running_stats=True)), modules/discriminators.py:113-128,160-162.
+#include <algorithm>
+
+#include "hip_util.h"
+
+namespace swn {
+
+namespace {
+
+constexpr double BN_EPS = 1e-5, BN_MOMENTUM = 0.1;
+
+__device__ __forceinline__ float bn_act_grad(float z, int act) {      // through the activation's INPUT
+  switch (act) {
+    case ACT_LRELU: return z > 0.f ? 1.f : 0.2f;
+    case ACT_RELU: return z > 0.f ? 1.f : 0.f;
+    case ACT_TANH: { const float th = tanhf(z); return 1.f - th * th; }
+    default: return 1.f;
+  }
+}
+
+struct BNp {
+  const float* x; int xcs;
+  float* y; int ycs;              // fwd: y ; bwd: dx
+  const float* dy; int dycs;      // bwd only
+  const float *gamma, *beta;
+  float *running_mean, *running_var;
+  long long* nbt;
+  float* stats;                   // [groups][C][2] (mean, rstd)
+  float* fold;                    // [groups][2][C]: scale = gamma * rstd, shift = beta - mean * scale
+  double* partial;                // [N][nchunk][C][2]
+  double* coef;                   // bwd: [groups][C][2] = sum(dy') / M, sum(dy' xh) / M
+  float *dgamma, *dbeta;
+  int N, HW, C, nchunk, chunk, groups, act;
+  float* amax_out;
+};
+
+// partial sums over a pixel chunk of one image: MODE 0 -> (sum x, sum x^2); MODE 1 -> (sum dy', sum dy' * xh), dy' = dy * act'(z)
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_partial_kernel(BNp p) {
+  __shared__ double red[256 * 8];
+  const int C4 = p.C >> 2;
+  const int rows = 256 / C4;
+  const int t = threadIdx.x, tx = t % C4, ty = t / C4;
+  const int n = blockIdx.y, ch = blockIdx.x;
+  const int g = n / (p.N / p.groups);
+  const int c0 = ch * p.chunk, c1 = min(p.HW, c0 + p.chunk);
+  double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+  if (ty < rows) {
+    float mean[4] = {0, 0, 0, 0}, rstd[4] = {1, 1, 1, 1}, sc[4] = {1, 1, 1, 1}, sh[4] = {0, 0, 0, 0};
+    if (MODE == 1) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const size_t gc = (size_t)g * p.C + tx * 4 + j;
+        mean[j] = p.stats[gc * 2]; rstd[j] = p.stats[gc * 2 + 1];
+        sc[j] = p.fold[(size_t)g * 2 * p.C + tx * 4 + j]; sh[j] = p.fold[((size_t)g * 2 + 1) * p.C + tx * 4 + j];
+      }
+    }
+    for (int pix = c0 + ty; pix < c1; pix += rows) {
+      const size_t e = (size_t)n * p.HW + pix;
+      const float4 xv = *reinterpret_cast<const float4*>(p.x + e * p.xcs + tx * 4);
+      const float xa[4] = {xv.x, xv.y, xv.z, xv.w};
+      if (MODE == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s[j] += xa[j]; ss[j] += (double)xa[j] * xa[j]; }
+      } else {
+        const float4 gv = *reinterpret_cast<const float4*>(p.dy + e * p.dycs + tx * 4);
+        const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float z = xa[j] * sc[j] + sh[j];                        // the forward's value (selects the activation branch)
+          const float d = ga[j] * bn_act_grad(z, p.act);
+          s[j] += d; ss[j] += (double)d * (((double)xa[j] - (double)mean[j]) * (double)rstd[j]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { red[t * 8 + j] = s[j]; red[t * 8 + 4 + j] = ss[j]; }
+  __syncthreads();
+  if (ty == 0) {
+    for (int r = 1; r < rows; ++r)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[t * 8 + j] += red[(r * C4 + tx) * 8 + j];
+    double* o = p.partial + (((size_t)n * p.nchunk + ch) * p.C + tx * 4) * 2;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { o[j * 2] = red[t * 8 + j]; o[j * 2 + 1] = red[t * 8 + 4 + j]; }
+  }
+}
+
+// 16 channels x 16 lanes per block.  Group by group, in group order: each lane sums every 16th (image, chunk) partial of the group,
+// then lane 0 sums the 16 lanes in a fixed order (deterministic) and finishes the group -- MODE 0: statistics, the folded scale /
+// shift and the running update (group 1's update sees group 0's); MODE 1: the backward coefficients and d gamma / d beta, summed
+// over the groups in group order.
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_finalize_kernel(BNp p) {
+  __shared__ double red[256 * 2];
+  const int cl = threadIdx.x & 15, ln = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl;
+  const int cnt = (p.N / p.groups) * p.nchunk;
+  const double M = (double)(p.N / p.groups) * p.HW;
+  double dg = 0, db = 0;
+  for (int g = 0; g < p.groups; ++g) {
+    double a = 0, b = 0;
+    if (c < p.C)
+      for (int i = ln; i < cnt; i += 16) {
+        const double* o = p.partial + (((size_t)g * cnt + i) * p.C + c) * 2;
+        a += o[0]; b += o[1];
+      }
+    red[threadIdx.x * 2] = a; red[threadIdx.x * 2 + 1] = b;
+    __syncthreads();
+    if (ln == 0 && c < p.C) {
+      double A = 0, B = 0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { A += red[(j * 16 + cl) * 2]; B += red[(j * 16 + cl) * 2 + 1]; }
+      const size_t gc = (size_t)g * p.C + c;
+      if (MODE == 0) {
+        const double mean = A / M;
+        double var = B / M - mean * mean;
+        if (var < 0) var = 0;
+        const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + BN_EPS));
+        p.stats[gc * 2] = meanf; p.stats[gc * 2 + 1] = rstdf;
+        const float scale = (float)((double)p.gamma[c] * (double)rstdf);
+        p.fold[(size_t)g * 2 * p.C + c] = scale;
+        p.fold[((size_t)g * 2 + 1) * p.C + c] = (float)((double)p.beta[c] - mean * (double)scale);
+        if (p.running_mean) {
+          p.running_mean[c] = (float)((1.0 - BN_MOMENTUM) * (double)p.running_mean[c] + BN_MOMENTUM * mean);
+          p.running_var[c] = (float)((1.0 - BN_MOMENTUM) * (double)p.running_var[c] + BN_MOMENTUM * var * (M / (M - 1.0)));
+        }
+      } else {
+        p.coef[gc * 2] = A / M; p.coef[gc * 2 + 1] = B / M;
+        db += A; dg += B;
+      }
+    }
+    __syncthreads();
+  }
+  if (MODE == 0 && p.nbt && blockIdx.x == 0 && threadIdx.x == 0) *p.nbt += p.groups;
+  if (MODE == 1 && p.dgamma && ln == 0 && c < p.C) { p.dgamma[c] = (float)dg; p.dbeta[c] = (float)db; }
+}
+
+// eval mode: scale / shift from the running buffers (one group)
+__global__ void bn_fold_running_kernel(BNp p) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= p.C) return;
+  const float scale = (float)((double)p.gamma[c] / sqrt((double)p.running_var[c] + BN_EPS));
+  p.fold[c] = scale;
+  p.fold[p.C + c] = (float)((double)p.beta[c] - (double)p.running_mean[c] * (double)scale);
+}
+
+__global__ __launch_bounds__(256) void bn_apply_kernel(BNp p) {
+  const int C4 = p.C >> 2;
+  const size_t total = (size_t)p.N * p.HW * C4;
+  const int npg = p.N / p.groups;
+  float am = 0.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = i / C4;
+    const int c = (int)(i - e * C4) * 4;
+    const int g = (int)(e / p.HW) / npg;
+    const float4 xv = *reinterpret_cast<const float4*>(p.x + e * p.xcs + c);
+    const float4 sc = *reinterpret_cast<const float4*>(p.fold + (size_t)g * 2 * p.C + c);
+    const float4 sh = *reinterpret_cast<const float4*>(p.fold + ((size_t)g * 2 + 1) * p.C + c);
+    const float4 o4 = make_float4(act_apply(xv.x * sc.x + sh.x, p.act), act_apply(xv.y * sc.y + sh.y, p.act),
+                                  act_apply(xv.z * sc.z + sh.z, p.act), act_apply(xv.w * sc.w + sh.w, p.act));
+    *reinterpret_cast<float4*>(p.y + e * p.ycs + c) = o4;
+    am = fmaxf(am, f4amax(o4));
+  }
+  amax_fold(am, p.amax_out);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BNp p) {
+  const int C4 = p.C >> 2;
+  const size_t total = (size_t)p.N * p.HW * C4;
+  const int npg = p.N / p.groups;
+  float am = 0.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = i / C4;
+    const int c = (int)(i - e * C4) * 4;
+    const int g = (int)(e / p.HW) / npg;
+    const float4 xv = *reinterpret_cast<const float4*>(p.x + e * p.xcs + c);
+    const float4 gv = *reinterpret_cast<const float4*>(p.dy + e * p.dycs + c);
+    const float4 sc = *reinterpret_cast<const float4*>(p.fold + (size_t)g * 2 * p.C + c);
+    const float4 sh = *reinterpret_cast<const float4*>(p.fold + ((size_t)g * 2 + 1) * p.C + c);
+    const float xa[4] = {xv.x, xv.y, xv.z, xv.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w};
+    const float sca[4] = {sc.x, sc.y, sc.z, sc.w}, sha[4] = {sh.x, sh.y, sh.z, sh.w};
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const size_t gc = (size_t)g * p.C + c + j;
+      const float mean = p.stats[gc * 2], rstd = p.stats[gc * 2 + 1];
+      const double m1 = p.coef[gc * 2], m2 = p.coef[gc * 2 + 1];
+      const float d = ga[j] * bn_act_grad(xa[j] * sca[j] + sha[j], p.act);
+      // d - mean(d) - xh * mean(d xh) cancels (norm_act.hip norm_act_bwd_apply_kernel): combined in double, the pass is HBM-bound
+      o[j] = (float)((double)sca[j] * ((double)d - m1 - (((double)xa[j] - (double)mean) * (double)rstd) * m2));
+    }
+    const float4 o4 = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(p.y + e * p.ycs + c) = o4;
+    am = fmaxf(am, f4amax(o4));
+  }
+  amax_fold(am, p.amax_out);
+}
+
+inline unsigned bn_grid(size_t total) {
+  const size_t b = (total + 255) / 256;
+  return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), 256 * 16);
+}
+
+void bn_check_view(const TView& v, const char* what) {
+  if (v.C % 4 || v.cs % 4 || ((uintptr_t)v.p & 15)) throw Error(1, std::string(what) + ": view not 16-byte tileable");
+}
+
+BNp bn_common(const TView& x, int groups, const char* what) {
+  bn_check_view(x, what);
+  if (x.C > 1024) throw Error(1, std::string(what) + ": C > 1024 unsupported");
+  if (groups < 1 || groups > 2 || x.N < groups || x.N % groups) throw Error(1, std::string(what) + ": groups must be 1 or 2 and divide the batch");
+  BNp p{};
+  p.x = x.p; p.xcs = x.cs; p.N = x.N; p.HW = x.H * x.W; p.C = x.C; p.groups = groups;
+  return p;
+}
+
+// pixels per statistics block: ~1024 blocks in flight, at least 4 pixels per thread row, a whole number of thread rows per chunk
+void batch_norm_plan_chunks(int HW, int N, int C, int& nchunk, int& chunk) {
+  const int rows = std::max(1, 256 / (C / 4));
+  const int want = std::max(1, 1024 / std::max(N, 1));
+  const int maxchunks = std::max(1, HW / (rows * 4));
+  nchunk = std::min(std::min(want, maxchunks), 256);
+  chunk = round_up(ceil_div(HW, nchunk), rows);
+  nchunk = ceil_div(HW, chunk);
+}
+
+}  // namespace
+
+void batch_norm_fwd(Stream& s, const BatchNormArgs& a) {
+  BNp p = bn_common(a.x, a.training ? a.groups : 1, "batch_norm_fwd x");
+  bn_check_view(a.y, "batch_norm_fwd y");
+  if (!a.gamma || !a.beta || !a.fold) throw Error(1, "batch_norm_fwd: gamma, beta and the fold buffer are required");
+  if (((uintptr_t)a.fold & 15)) throw Error(1, "batch_norm_fwd: fold buffer not 16-byte aligned");
+  p.y = a.y.p; p.ycs = a.y.cs; p.gamma = a.gamma; p.beta = a.beta; p.act = a.act;
+  p.running_mean = a.running_mean; p.running_var = a.running_var; p.nbt = a.num_batches_tracked;
+  p.stats = a.stats; p.fold = a.fold; p.amax_out = a.amax_out;
+  if (a.training) {
+    if (!a.stats) throw Error(1, "batch_norm_fwd: stats buffer required in training mode");
+    if ((bool)a.running_mean != (bool)a.running_var) throw Error(1, "batch_norm_fwd: running_mean and running_var go together");
+    if ((size_t)(p.N / p.groups) * p.HW <= 1)
+      throw Error(1, "Expected more than 1 value per channel when training, got input size (" + std::to_string(p.N / p.groups) + ", " +
+                         std::to_string(p.C) + ", " + std::to_string(a.x.H) + ", " + std::to_string(a.x.W) + ")");
+    if (a.partial_in) {
+      // the producing conv's epilogue left the partial sums (ops.h ConvFwdArgs::stat_partial): no statistics pass over x
+      if (a.partial_chunks <= 0 || p.HW % a.partial_chunks) throw Error(1, "batch_norm_fwd: bad partial_chunks");
+      p.nchunk = a.partial_chunks; p.chunk = p.HW / a.partial_chunks;
+      p.partial = const_cast<double*>(a.partial_in);
+      if (route_on()) route_note("batch_norm_fwd[statistics from the conv epilogue, bn_finalize_kernel, bn_apply_kernel]");
+    } else {
+      batch_norm_plan_chunks(p.HW, p.N, p.C, p.nchunk, p.chunk);
+      p.partial = reinterpret_cast<double*>(s.ws);
+      if ((size_t)p.N * p.nchunk * p.C * 16 > s.ws_bytes) throw Error(1, "batch_norm_fwd: workspace too small");
+      if (route_on()) route_note("batch_norm_fwd[bn_partial_kernel, bn_finalize_kernel, bn_apply_kernel]");
+      hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(p.nchunk, p.N), dim3(256), 0, hs(s), p);
+    }
+    hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(ceil_div(p.C, 16)), dim3(256), 0, hs(s), p);
+  } else {
+    if (!a.running_mean || !a.running_var) throw Error(1, "batch_norm_fwd: eval mode needs the running buffers");
+    if (route_on()) route_note("batch_norm_fwd[eval: bn_fold_running_kernel, bn_apply_kernel]");
+    hipLaunchKernelGGL(bn_fold_running_kernel, dim3(ceil_div(p.C, 256)), dim3(256), 0, hs(s), p);
+  }
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_grid((size_t)p.N * p.HW * (p.C / 4))), dim3(256), 0, hs(s), p);
+  check_launch("batch_norm_fwd");
+}
+
+void batch_norm_bwd(Stream& s, const BatchNormBwdArgs& a) {
+  BNp p = bn_common(a.x, a.groups, "batch_norm_bwd x");
+  bn_check_view(a.dy, "batch_norm_bwd dy"); bn_check_view(a.dx, "batch_norm_bwd dx");
+  if (!a.stats || !a.fold) throw Error(1, "batch_norm_bwd: the forward's stats and fold buffers are required");
+  if ((bool)a.dgamma != (bool)a.dbeta) throw Error(1, "batch_norm_bwd: dgamma and dbeta go together");
+  p.dy = a.dy.p; p.dycs = a.dy.cs; p.y = a.dx.p; p.ycs = a.dx.cs; p.act = a.act;
+  p.stats = const_cast<float*>(a.stats); p.fold = const_cast<float*>(a.fold);
+  p.dgamma = a.dgamma; p.dbeta = a.dbeta; p.amax_out = a.amax_out;
+  batch_norm_plan_chunks(p.HW, p.N, p.C, p.nchunk, p.chunk);
+  p.partial = reinterpret_cast<double*>(s.ws);
+  const size_t pbytes = ((size_t)p.N * p.nchunk * p.C * 16 + 255) / 256 * 256;
+  p.coef = reinterpret_cast<double*>(s.ws + pbytes);
+  if (pbytes + (size_t)p.groups * p.C * 16 > s.ws_bytes) throw Error(1, "batch_norm_bwd: workspace too small");
+  if (route_on()) route_note(a.dgamma ? "batch_norm_bwd[bn_partial_kernel, bn_finalize_kernel, bn_bwd_apply_kernel]"
+                                      : "batch_norm_bwd[bn_partial_kernel, bn_finalize_kernel (no parameter gradients), bn_bwd_apply_kernel]");
+  hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(p.nchunk, p.N), dim3(256), 0, hs(s), p);
+  hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(ceil_div(p.C, 16)), dim3(256), 0, hs(s), p);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_grid((size_t)p.N * p.HW * (p.C / 4))), dim3(256), 0, hs(s), p);
+  check_launch("batch_norm_bwd");
+}
+
+}  // namespace swn

@@ -3,6 +3,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/swapnet_hip.h"
 #include <cstdlib>
@@ -27,7 +28,7 @@ struct swn_model {
   std::shared_ptr<Model> sharer;    // the model whose arenas this one uses (swn_model_create_shared): outlives it
   std::shared_ptr<Model> m;
   // what it was created with (a sharing model is created like its sharer, at another batch size)
-  int kind = 0, is_train = 1, num_roi = 12, body_channels = 3, cloth_channels = 19, patchgan_layers = 3;
+  int kind = 0, is_train = 1, num_roi = 12, body_channels = 3, cloth_channels = 19, patchgan_layers = 3, patchgan_norm = 0;
   float dropout = 0.5f;
 };
 struct swn_pipeline {
@@ -106,6 +107,13 @@ int swn_ctx_set_patchgan_layers(swn_ctx* ctx, int n_layers) {
     ctx->c->patchgan_layers = n_layers;
   });
 }
+int swn_ctx_set_patchgan_norm(swn_ctx* ctx, int kind) {
+  return guard([&] {
+    REQUIRE(ctx, "ctx is NULL");
+    REQUIRE(kind >= 0 && kind <= 2, "normalization layer is not found (0 instance, 1 batch, 2 none)");
+    ctx->c->patchgan_norm = kind;
+  });
+}
 int swn_ctx_sync(swn_ctx* ctx) {
   return guard([&] { REQUIRE(ctx, "ctx is NULL"); stream_sync(ctx->c->s); });
 }
@@ -142,7 +150,7 @@ int swn_warp_model_create_ex(swn_ctx* ctx, int batch, int height, int width, int
     h->keep = ctx->box;
     h->m.reset(create_warp_model(*ctx->c, batch, height, width, is_train != 0, dropout, body_channels, cloth_channels));
     h->kind = 0; h->is_train = is_train != 0; h->dropout = dropout; h->body_channels = body_channels; h->cloth_channels = cloth_channels;
-    h->patchgan_layers = ctx->c->patchgan_layers;
+    h->patchgan_layers = ctx->c->patchgan_layers; h->patchgan_norm = ctx->c->patchgan_norm;
     *out = h.release();
   });
 }
@@ -177,15 +185,16 @@ int swn_model_create_shared(swn_model* sharer, int batch, int height, int width,
     h->sharer = root;
     h->kind = sharer->kind; h->is_train = sharer->is_train; h->dropout = sharer->dropout; h->num_roi = sharer->num_roi;
     h->body_channels = sharer->body_channels; h->cloth_channels = sharer->cloth_channels; h->patchgan_layers = sharer->patchgan_layers;
-    const int layers_was = c.patchgan_layers;
-    c.patchgan_layers = sharer->patchgan_layers;
+    h->patchgan_norm = sharer->patchgan_norm;
+    const int layers_was = c.patchgan_layers, norm_was = c.patchgan_norm;
+    c.patchgan_layers = sharer->patchgan_layers; c.patchgan_norm = sharer->patchgan_norm;
     try {
       if (h->kind == 0)
         h->m.reset(create_warp_model(c, batch, height, width, h->is_train != 0, h->dropout, h->body_channels, h->cloth_channels, root.get()));
       else
         h->m.reset(create_texture_model(c, batch, height, width, h->is_train != 0, h->num_roi, h->cloth_channels, root.get()));
-    } catch (...) { c.patchgan_layers = layers_was; throw; }
-    c.patchgan_layers = layers_was;
+    } catch (...) { c.patchgan_layers = layers_was; c.patchgan_norm = norm_was; throw; }
+    c.patchgan_layers = layers_was; c.patchgan_norm = norm_was;
     h->m->hyper = root->hyper;
     *out = h.release();
   });
@@ -213,8 +222,8 @@ int swn_model_set_hyper(swn_model* m, const swn_hyper* h) {
     y.d_b1 = h->d_b1 >= 0.f ? h->d_b1 : h->b1; y.d_b2 = h->d_b2 >= 0.f ? h->d_b2 : h->b2;
     REQUIRE(h->gp_mode >= 0 && h->gp_mode <= 3, "gradient penalty mode not implemented");
     REQUIRE(h->gp_mode == 0 || m->m->supports_gradient_penalty(),
-            "gradient penalty modes are not implemented for the texture model (the reference's call fails there too) nor for the "
-            "1x1 PixelDiscriminator");
+            "gradient penalty modes are not implemented for the texture model (the reference's call fails there too), for the "
+            "1x1 PixelDiscriminator, nor for a discriminator under --norm batch / none (the second-order pass walks InstanceNorm)");
     y.gp_mode = h->gp_mode; y.lambda_gp = h->lambda_gp;
   });
 }
@@ -293,6 +302,57 @@ int swn_model_param_get(swn_model* m, int net, int which, const char* name, floa
     if (d.is_bias) dev_copy(s, dst, a.base(which) + d.off, d.n_logical * sizeof(float));
     else unpack_weight(s, d.ws, a.base(which) + d.off, dst);
   });
+}
+// ---- state-dict buffers: the running statistics of the discriminator's BatchNorm sites -------------------------------------
+static std::vector<Model::BNSite>& sites_of(swn_model* m, int net) {
+  static std::vector<Model::BNSite> none;
+  arena_of(m, net);                      // (validates the model and the network)
+  return net == 1 ? m->m->bn_sites() : none;
+}
+static const char* const kBufferNames[3] = {"running_mean", "running_var", "num_batches_tracked"};
+static void* find_buffer(swn_model* m, int net, const char* name, size_t* bytes) {
+  REQUIRE(name, "name is NULL");
+  const std::string full(name);
+  for (Model::BNSite& s : sites_of(m, net))
+    for (int k = 0; k < 3; ++k)
+      if (full == s.name + "." + kBufferNames[k]) {
+        *bytes = k == 2 ? sizeof(int64_t) : (size_t)s.C * sizeof(float);
+        return k == 0 ? (void*)s.run.mean : k == 1 ? (void*)s.run.var : (void*)s.run.count;
+      }
+  throw Error(1, std::string("unknown buffer ") + name);
+}
+int swn_model_buffer_count(swn_model* m, int net, int* out) {
+  return guard([&] { REQUIRE(out, "NULL"); *out = 3 * (int)sites_of(m, net).size(); });
+}
+int swn_model_buffer_info(swn_model* m, int net, int index, char* name, int name_len, int* numel, int* is_int64) {
+  return guard([&] {
+    auto& sites = sites_of(m, net);
+    REQUIRE(index >= 0 && index < 3 * (int)sites.size(), "buffer index out of range");
+    const Model::BNSite& s = sites[index / 3];
+    const std::string full = s.name + "." + kBufferNames[index % 3];
+    if (name && name_len > 0) { std::strncpy(name, full.c_str(), name_len - 1); name[name_len - 1] = 0; }
+    if (numel) *numel = index % 3 == 2 ? 1 : s.C;
+    if (is_int64) *is_int64 = index % 3 == 2;
+  });
+}
+int swn_model_buffer_set(swn_model* m, int net, const char* name, const void* src) {
+  return guard([&] {
+    REQUIRE(src, "NULL argument");
+    size_t bytes = 0;
+    void* dst = find_buffer(m, net, name, &bytes);
+    dev_copy(m->m->ctx->s, dst, src, bytes);
+  });
+}
+int swn_model_buffer_get(swn_model* m, int net, const char* name, void* dst) {
+  return guard([&] {
+    REQUIRE(dst, "NULL argument");
+    size_t bytes = 0;
+    const void* src = find_buffer(m, net, name, &bytes);
+    dev_copy(m->m->ctx->s, dst, src, bytes);
+  });
+}
+int swn_model_set_discriminate_mode(swn_model* m, int training) {
+  return guard([&] { REQUIRE(m, "NULL argument"); m->m->discriminate_training = training != 0; });
 }
 int swn_model_optim_step_get(swn_model* m, int net, int* step) {
   return guard([&] { REQUIRE(step, "NULL"); *step = arena_of(m, net).step; });
@@ -707,6 +767,81 @@ int swn_op_instance_norm_act_bwd(swn_ctx* ctx, const float* x, const float* dy, 
     net.backward(false, true);
     nhwc_to_nchw(tmp.s, xv.g, dx, c);
     stream_sync(tmp.s);
+  });
+}
+// BatchNorm2d + activation as one call (tests, tools/bn_shapes.py): the layer of Net::batch_norm_act on NCHW tensors
+static void bn_op_build(Ctx& tmp, ParamArena& A, Net& net, Var& xv, Var& yv, int n, int c, int h, int w, int groups, int act,
+                        const Net::BNBuffers& run, const float* weight, const float* bias) {
+  xv = net.alloc_var(n, h, w, c, true); yv = net.alloc_var(n, h, w, c, true);
+  net.batch_norm_act("bn", xv, yv, act, groups, run);
+  A.allocate(tmp);
+  net.finalize({});
+  dev_copy(tmp.s, A.w + A.params[A.index.at("bn.weight")].off, weight, c * sizeof(float));
+  dev_copy(tmp.s, A.w + A.params[A.index.at("bn.bias")].off, bias, c * sizeof(float));
+}
+int swn_op_batch_norm_act(swn_ctx* ctx, const float* x, int n, int c, int h, int w, int groups, int act, int training,
+                          const float* weight, const float* bias, float* running_mean, float* running_var,
+                          int64_t* num_batches_tracked, float* y, float* save_stats) {
+  return guard([&] {
+    REQUIRE(ctx && x && y && weight && bias && c % 4 == 0, "bad argument (C must be a multiple of 4)");
+    REQUIRE(training || (running_mean && running_var), "eval mode needs the running buffers");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Var xv, yv;
+    Net::BNBuffers run{running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked)};
+    bn_op_build(tmp, A, net, xv, yv, n, c, h, w, groups, act, run, weight, bias);
+    net.bn_training = training != 0;
+    nchw_to_nhwc(tmp.s, x, n, c, h, w, xv.v);
+    net.forward();
+    nhwc_to_nchw(tmp.s, yv.v, y, c);
+    if (save_stats && training) dev_copy(tmp.s, save_stats, net.last_stats, (size_t)groups * c * 2 * sizeof(float));
+    stream_sync(tmp.s);
+  });
+}
+int swn_op_batch_norm_act_bwd(swn_ctx* ctx, const float* x, const float* dy, int n, int c, int h, int w, int groups, int act,
+                              const float* weight, const float* bias, float* dx, float* dweight, float* dbias) {
+  return guard([&] {
+    REQUIRE(ctx && x && dy && dx && weight && bias && c % 4 == 0, "bad argument (C must be a multiple of 4)");
+    REQUIRE((dweight != nullptr) == (dbias != nullptr), "dweight and dbias go together");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Var xv, yv;
+    bn_op_build(tmp, A, net, xv, yv, n, c, h, w, groups, act, Net::BNBuffers(), weight, bias);
+    nchw_to_nhwc(tmp.s, x, n, c, h, w, xv.v);
+    net.forward();
+    nchw_to_nhwc(tmp.s, dy, n, c, h, w, yv.g);
+    net.backward(dweight != nullptr, true);
+    nhwc_to_nchw(tmp.s, xv.g, dx, c);
+    if (dweight) {
+      dev_copy(tmp.s, dweight, A.g + A.params[A.index.at("bn.weight")].off, c * sizeof(float));
+      dev_copy(tmp.s, dbias, A.g + A.params[A.index.at("bn.bias")].off, c * sizeof(float));
+    }
+    stream_sync(tmp.s);
+  });
+}
+int swn_op_norm_act_time(swn_ctx* ctx, int kind, int what, const float* x, const float* dy, int n, int c, int h, int w, int groups,
+                         int act, int warmup, int iters, float* ms_out) {
+  return guard([&] {
+    REQUIRE(ctx && x && ms_out && c % 4 == 0 && (what == 0 || dy), "bad argument (C must be a multiple of 4; the backward pass needs dy)");
+    REQUIRE((kind == 0 || kind == 1) && (what == 0 || what == 1) && warmup >= 0 && iters >= 1 && iters <= 1000, "bad kind / what / iters");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Var xv = net.alloc_var(n, h, w, c, true), yv = net.alloc_var(n, h, w, c, true);
+    if (kind == 0) {
+      net.norm_act(xv, yv, true, act, 0.f);
+    } else {
+      // gamma = 1, beta = 0; fresh running buffers, updated by every forward pass like a training step's
+      float* run = static_cast<float*>(tmp.alloc((size_t)2 * c * sizeof(float) + 16));
+      net.batch_norm_act("bn", xv, yv, act, groups, Net::BNBuffers{run, run + c, reinterpret_cast<long long*>(run + 2 * c)});
+      A.allocate(tmp);
+      std::vector<float> ones(c, 1.f);
+      dev_upload(tmp.s, A.w + A.params[A.index.at("bn.weight")].off, ones.data(), c * sizeof(float));
+    }
+    net.finalize({});
+    nchw_to_nhwc(tmp.s, x, n, c, h, w, xv.v);
+    net.forward();
+    if (what == 1) nchw_to_nhwc(tmp.s, dy, n, c, h, w, yv.g);
+    time_launches(tmp.s, warmup, iters, [&] { if (what == 0) net.forward(); else net.backward(true, true); }, ms_out);
   });
 }
 int swn_op_affine_gather(swn_ctx* ctx, const float* src, float* dst, int b, int c, int h, int w, const double* maps,

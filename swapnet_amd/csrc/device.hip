@@ -3,6 +3,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <functional>
+#include <vector>
 
 namespace swn {
 
@@ -97,6 +99,16 @@ void event_destroy(void* ev) {
 void event_record(void* ev, Stream& s) { SWN_HIP_CHECK(hipEventRecord((hipEvent_t)ev, hs(s))); }
 void stream_wait_event(Stream& s, void* ev) { SWN_HIP_CHECK(hipStreamWaitEvent(hs(s), (hipEvent_t)ev, 0)); }
 int is_device_build() { return 1; }
+void time_launches(Stream& s, int warmup, int iters, const std::function<void()>& enqueue, float* ms_host) {
+  std::vector<hipEvent_t> ev(iters + 1);
+  for (auto& e : ev) SWN_HIP_CHECK(hipEventCreate(&e));
+  for (int i = 0; i < warmup; ++i) enqueue();
+  SWN_HIP_CHECK(hipEventRecord(ev[0], hs(s)));
+  for (int i = 0; i < iters; ++i) { enqueue(); SWN_HIP_CHECK(hipEventRecord(ev[i + 1], hs(s))); }
+  SWN_HIP_CHECK(hipEventSynchronize(ev[iters]));
+  for (int i = 0; i < iters; ++i) SWN_HIP_CHECK(hipEventElapsedTime(&ms_host[i], ev[i], ev[i + 1]));
+  for (auto& e : ev) (void)hipEventDestroy(e);
+}
 
 void* stream_create_current() {
   hipStream_t st;

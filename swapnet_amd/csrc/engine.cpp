@@ -1137,6 +1137,49 @@ void Net::norm_act(const Var& raw, const Var& y, bool norm, int actf, float drop
   ops.push_back(std::move(op));
 }
 
+// ---- BatchNorm2d -> act (batch_norm.hip) -------------------------------------------------
+void Net::batch_norm_act(const std::string& name, const Var& raw, const Var& y, int actf, int groups, const BNBuffers& run) {
+  auto op = std::make_unique<Op>();
+  op->label = "batch_norm_act";
+  const int C = raw.v.C;
+  const size_t goff = arena.params[arena.add_bias(name + ".weight", C)].off;
+  const size_t boff = arena.params[arena.add_bias(name + ".bias", C)].off;
+  op->param_off = goff;
+  float* stats = static_cast<float*>(ctx.alloc((size_t)groups * C * 2 * sizeof(float)));
+  float* fold = static_cast<float*>(ctx.alloc((size_t)groups * C * 2 * sizeof(float)));
+  last_stats = stats;
+  note_act(actf, y.v);
+  const TView rv = raw.v, rg = raw.g, yv = y.v, yg = y.g;
+  const size_t ySlot = note_writer(y.vbase, true);
+  const bool do_bwd = y.has_grad && raw.has_grad;
+  const size_t gSlot = do_bwd ? note_writer(raw.gbase, true) : 0;
+  const double* partial_in = nullptr;
+  int partial_chunks = 0;
+  if (raw.v.H * raw.v.W > 1024 && raw.v.p == raw.vbase) {        // the producing conv's epilogue offers the partial sums (see norm_act)
+    auto it = conv_stats.find(raw.vbase);
+    if (it != conv_stats.end()) { *it->second.use = true; partial_in = it->second.partial; partial_chunks = it->second.chunks; }
+  }
+  op->fwd = [=](Net& n) {
+    BatchNormArgs a;
+    a.x = rv; a.y = yv; a.gamma = n.arena.w + goff; a.beta = n.arena.w + boff;
+    a.running_mean = run.mean; a.running_var = run.var; a.num_batches_tracked = run.count;
+    a.stats = stats; a.fold = fold; a.groups = groups; a.act = actf; a.training = n.bn_training ? 1 : 0;
+    a.amax_out = n.amax + ySlot;
+    if (n.bn_training) { a.partial_in = partial_in; a.partial_chunks = partial_chunks; }
+    batch_norm_fwd(n.ctx.s, a);
+  };
+  op->bwd = [=](Net& n, Op&, bool wgrad, bool) {
+    if (!do_bwd) return;
+    if (!n.bn_training) throw Error(1, "batch_norm_act: backward through the eval-mode forward is not supported");
+    BatchNormBwdArgs b;
+    b.dy = yg; b.x = rv; b.stats = stats; b.fold = fold; b.dx = rg; b.groups = groups; b.act = actf;
+    if (wgrad) { b.dgamma = n.arena.g + goff; b.dbeta = n.arena.g + boff; }
+    b.amax_out = n.amax + gSlot;
+    batch_norm_bwd(n.ctx.s, b);
+  };
+  ops.push_back(std::move(op));
+}
+
 void Net::act(const Var& x, const Var& y, int actf) {
   auto op = std::make_unique<Op>();
   op->label = "act";
@@ -1442,6 +1485,28 @@ void Model::optimizer_step(int net) {
   A.version += 1;
 }
 
+Net::BNBuffers Model::bn_site(const std::string& name, int C) {
+  for (BNSite& s : bn_sites())
+    if (s.name == name) {
+      if (s.C != C) throw Error(1, "BatchNorm site " + name + ": channel count differs from the arena owner's");
+      return s.run;
+    }
+  if (share_) throw Error(1, "shared model: the arena's owner has no BatchNorm site " + name);
+  bn_sites_.emplace_back();
+  BNSite& s = bn_sites_.back();
+  s.name = name; s.C = C; s.ones.assign(C, 1.f);
+  float* buf = static_cast<float*>(ctx->alloc((size_t)2 * C * sizeof(float) + 16));      // zero-filled: mean 0, count 0
+  s.run = Net::BNBuffers{buf, buf + C, reinterpret_cast<long long*>(buf + 2 * C)};
+  dev_upload(ctx->s, s.run.var, s.ones.data(), C * sizeof(float));
+  return s.run;
+}
+PatchganNorm Model::d_norm(int groups) {
+  PatchganNorm n;
+  n.kind = d_norm_; n.groups = groups;
+  n.site = [this](const std::string& name, int C) { return bn_site(name, C); };
+  return n;
+}
+
 void Model::discriminate(const float* x_nchw, float* pred_nchw) {
   if (!is_train || !D2) throw Error(1, "discriminate: the model has no discriminator (created with is_train = 0)");
   if (d_cimap_.empty()) throw Error(1, "discriminate: model did not publish its conditional-input channel map");
@@ -1449,7 +1514,7 @@ void Model::discriminate(const float* x_nchw, float* pred_nchw) {
     AllocScope mine(*ctx, owned_allocs);
     D3_ = std::make_unique<Net>(*ctx, arenaD);
     d3_in_ = D3_->alloc_var(B, H, W, (int)d_cimap_.size(), false);
-    d3_pred_ = build_patchgan(*D3_, d3_in_, d_layers_, d_cimap_);
+    d3_pred_ = build_patchgan(*D3_, d3_in_, d_layers_, d_cimap_, 0, d_norm(1));
     D3_->finalize({});
   }
   // scatter the reference-ordered channels into the buffer order: maximal runs of consecutive channels
@@ -1469,6 +1534,7 @@ void Model::discriminate(const float* x_nchw, float* pred_nchw) {
     b0 += len;
   }
   D3_->training = false;
+  D3_->bn_training = discriminate_training;
   D3_->refresh_dgrad();
   D3_->forward();
   nhwc_to_nchw(ctx->s, d3_pred_.v, pred_nchw, 1);
@@ -1650,6 +1716,18 @@ void Model::step(const float labels[3], bool training, uint64_t seed) {
   }
   backward_G(labels[2]);
   optimizer_step(0);
+}
+
+// Host fallbacks of the BatchNorm launchers (ops.h).  Weak: the device library links batch_norm.hip, whose definitions take their
+// place; the host simulator has none, so a BatchNorm site there fails with the library's "not implemented" error.
+__attribute__((weak)) void batch_norm_fwd(Stream&, const BatchNormArgs&) {
+  throw Error(1, "batch_norm_fwd: BatchNorm is not implemented on the host simulator (HIP kernel only)");
+}
+__attribute__((weak)) void batch_norm_bwd(Stream&, const BatchNormBwdArgs&) {
+  throw Error(1, "batch_norm_bwd: BatchNorm is not implemented on the host simulator (HIP kernel only)");
+}
+__attribute__((weak)) void time_launches(Stream&, int, int, const std::function<void()>&, float*) {
+  throw Error(1, "time_launches: device timing is not implemented on the host simulator");
 }
 
 }  // namespace swn

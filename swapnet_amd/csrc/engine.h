@@ -61,6 +61,12 @@ struct Ctx {
   // discriminators.define_D(..., n_layers_D) (modules/discriminators.py:45-88, base_gan.py:147): stride-2 levels of the PatchGAN of
   // every model created on this context afterwards (3 = the reference's "basic" 70x70 PatchGAN)
   int patchgan_layers = 3;
+  // discriminators.define_D(..., norm) (modules/discriminators.py:77, modules/__init__.py:53-74; base_gan.py:147): the norm layer of the
+  // discriminator of every WARP model created on this context afterwards -- 0 instance (the reference's default), 1 batch
+  // (BatchNorm2d, affine, running statistics: Net::batch_norm_act), 2 none (identity).  Under 1 and 2 the inner convs have no bias
+  // (use_bias is true only under InstanceNorm2d, :104-107,151-154).  The texture stage's generator takes the same flag in the
+  // reference and has no BatchNorm form here yet: texture models refuse a non-instance kind.
+  int patchgan_norm = 0;
   explicit Ctx(void* stream, size_t ws_bytes);
   explicit Ctx(const Stream& shared);      // borrows stream + workspace of another context
   bool owns_ws = true;
@@ -247,6 +253,13 @@ class Net {
             const std::vector<int32_t>* cimap = nullptr, bool x_is_input = false, int dgrad_C = 0);
   void convT(const std::string& name, const Var& x, const Var& y, int Co, bool bias);
   void norm_act(const Var& raw, const Var& y, bool norm, int act, float drop_p, const Var* residual = nullptr);
+  // [BatchNorm2d] -> act (ops.h batch_norm_fwd): gamma / beta are the arena parameters `name`.weight / `name`.bias (so the fused
+  // optimizer update, weight decay, the gradient exchange and the state dict cover them like any bias); the running statistics
+  // belong to the caller, who hands the same BNBuffers to every net that shares the site.  groups: see ops.h.  The op follows
+  // bn_training (torch's train() / eval()); its backward skips d gamma / d beta when the pass takes no weight gradients.
+  struct BNBuffers { float* mean = nullptr; float* var = nullptr; long long* count = nullptr; };
+  bool bn_training = true;
+  void batch_norm_act(const std::string& name, const Var& raw, const Var& y, int act, int groups, const BNBuffers& run);
   void act(const Var& x, const Var& y, int act);
   void upsample(const Var& x, const Var& y, int factor);
   void maxpool(const Var& x, const Var& y);
@@ -295,7 +308,15 @@ class Net {
 void build_warp_generator(Net& net, const Var& body, const Var& cloth, const Var& out, float dropout, int body_channels = 3,
                           int cloth_channels = 19);
 // in_grad_channels > 0: only the first that many channels of the conditional input need a gradient (the generator's output)
-Var build_patchgan(Net& net, const Var& x, int n_layers, const std::vector<int32_t>& cimap, int in_grad_channels = 0);
+// norm: the discriminator's norm layer (Ctx::patchgan_norm).  kind 1: every norm site `model.K` / `net.3` becomes a batch_norm_act
+// over `groups` runs of the batch, with gamma / beta in the net's arena and the running buffers handed out by `site(name, C)`
+// (the model: nets bound to one arena share the buffers)
+struct PatchganNorm {
+  int kind = 0, groups = 1;
+  std::function<Net::BNBuffers(const std::string& name, int C)> site;
+};
+Var build_patchgan(Net& net, const Var& x, int n_layers, const std::vector<int32_t>& cimap, int in_grad_channels = 0,
+                   const PatchganNorm& norm = PatchganNorm());
 void build_texture_generator(Net& net, const Var& tex, const float* rois_dev, int num_roi, const Var& cloth_cat,
                              const Var& unet_in, const Var& out, int img_size, int cloth_channels = 19);
 // img: the image buffer (>= 4 channels, RGB in the first three; 16 channels put conv1_1 on the ring kernel) -- its gradient, if any,
@@ -462,8 +483,22 @@ class Model {
   Var d3_in_, d3_pred_;
   std::vector<int32_t> d_cimap_;  // buffer channel -> reference channel of the conditional D input (set by the model)
   int d_layers_ = 3;              // PatchGAN depth the model was built with (Ctx::patchgan_layers at construction)
+  int d_norm_ = 0;                // ... and its norm layer (Ctx::patchgan_norm at construction)
  public:
   int patchgan_layers() const { return d_layers_; }
+  int patchgan_norm() const { return d_norm_; }
+  // Running statistics of the discriminator's BatchNorm sites (state-dict buffers `name`.running_mean / .running_var /
+  // .num_batches_tracked): neither optimised nor exchanged, so they live outside the parameter arena.  Owned by the model that
+  // owns the arena; D2 (2B images, two groups), D1 and the discriminate() instance of it and of every sharing model update the same
+  // buffers -- per step in the reference's order: fake run, real run, then the fakes through the updated D.
+  struct BNSite { std::string name; int C = 0; Net::BNBuffers run; std::vector<float> ones; };
+  std::vector<BNSite> bn_sites_;  // the arena owner's
+  std::vector<BNSite>& bn_sites() { return share_ ? share_->bn_sites() : bn_sites_; }
+  Net::BNBuffers bn_site(const std::string& name, int C);      // finds the site; the arena's owner creates it (mean 0, var 1, count 0)
+  PatchganNorm d_norm(int groups);
+  // discriminate(): BatchNorm with batch statistics and a running update (nn.Module.train(), the default) or with the running
+  // buffers (eval())
+  bool discriminate_training = true;
   ParamArena& arena(int net) { return net == 0 ? arenaG : arenaD; }
   virtual ParamArena* arena_ptr(int net) {
     if (net == 0) return &arenaG;

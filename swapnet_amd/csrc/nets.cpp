@@ -92,11 +92,25 @@ void build_warp_generator(Net& n, const Var& body, const Var& cloth, const Var& 
 }
 
 // ---------------------------------------------------------------------------------------
-// NLayerDiscriminator under instance norm (modules/discriminators.py:91-136): all convs
-// carry a bias (:103-106).  Returns the 1-channel prediction map (C padded to 4).
+// NLayerDiscriminator (modules/discriminators.py:91-136).  Under instance norm all convs carry a bias (:103-106); under batch
+// norm and under no norm (modules/__init__.py:62-72) the convs in front of a norm layer have none -- use_bias is true only
+// for InstanceNorm2d -- and the first and last conv keep theirs (the PixelDiscriminator's last conv does not: :162 passes bias=use_bias).  Returns the 1-channel prediction map (C padded to 4).
 // ---------------------------------------------------------------------------------------
-Var build_patchgan(Net& n, const Var& x, int n_layers, const std::vector<int32_t>& cimap, int in_grad_channels) {
+// the norm layer + LeakyReLU(0.2) behind the conv `conv_name` = model.K / net.K: the norm module is entry K + 1 of the Sequential
+static void patchgan_norm_act(Net& n, const PatchganNorm& norm, const std::string& conv_name, const Var& raw, const Var& act) {
+  if (norm.kind == 1) {
+    const size_t dot = conv_name.rfind('.');
+    const std::string name = conv_name.substr(0, dot + 1) + std::to_string(std::stoi(conv_name.substr(dot + 1)) + 1);
+    n.batch_norm_act(name, raw, act, ACT_LRELU, norm.groups, norm.site(name, raw.v.C));
+  } else {
+    n.norm_act(raw, act, norm.kind == 0, ACT_LRELU, 0.f);
+  }
+}
+Var build_patchgan(Net& n, const Var& x, int n_layers, const std::vector<int32_t>& cimap, int in_grad_channels, const PatchganNorm& norm) {
   const int N = x.v.N;
+  if (norm.kind < 0 || norm.kind > 2) throw Error(1, "PatchGAN: norm kind must be 0 instance, 1 batch or 2 none");
+  if (norm.kind == 1 && !norm.site) throw Error(1, "PatchGAN: batch norm needs the running buffers' owner");
+  const bool inner_bias = norm.kind == 0;
   int ci = 0;
   for (int v : cimap) ci += v >= 0;
   const int ndf = 64;
@@ -108,11 +122,11 @@ Var build_patchgan(Net& n, const Var& x, int n_layers, const std::vector<int32_t
     n.taps["d0"] = a;
     Var raw = n.alloc_var(N, x.v.H, x.v.W, ndf * 2, true);
     Var act = n.alloc_var(N, x.v.H, x.v.W, ndf * 2, true);
-    n.conv("net.2", a, raw, CK_K1S1, ndf, ndf * 2, true, ACT_NONE);                                   // :160
-    n.norm_act(raw, act, true, ACT_LRELU, 0.f);                                                        // :161-162
+    n.conv("net.2", a, raw, CK_K1S1, ndf, ndf * 2, inner_bias, ACT_NONE);                             // :160
+    patchgan_norm_act(n, norm, "net.2", raw, act);                                                     // :161-162
     n.taps["d1"] = act;
     Var pred = n.alloc_var(N, x.v.H, x.v.W, 4, true);
-    n.conv("net.5", act, pred, CK_K1S1, ndf * 2, 1, true, ACT_NONE);                                   // :163
+    n.conv("net.5", act, pred, CK_K1S1, ndf * 2, 1, inner_bias, ACT_NONE);                             // :162 (bias=use_bias here too)
     n.taps["pred"] = pred;
     return pred;
   }
@@ -130,8 +144,8 @@ Var build_patchgan(Net& n, const Var& x, int n_layers, const std::vector<int32_t
     H /= 2; W /= 2;
     Var raw = n.alloc_var(N, H, W, ndf * mult, true);
     Var act = n.alloc_var(N, H, W, ndf * mult, true);
-    n.conv("model." + std::to_string(idx), a, raw, CK_K4S2, ndf * prev, ndf * mult, true, ACT_NONE);
-    n.norm_act(raw, act, true, ACT_LRELU, 0.f);
+    n.conv("model." + std::to_string(idx), a, raw, CK_K4S2, ndf * prev, ndf * mult, inner_bias, ACT_NONE);
+    patchgan_norm_act(n, norm, "model." + std::to_string(idx), raw, act);
     n.taps["d" + std::to_string(l)] = act;
     a = act; idx += 3;
   }
@@ -140,8 +154,8 @@ Var build_patchgan(Net& n, const Var& x, int n_layers, const std::vector<int32_t
   H -= 1; W -= 1;
   Var raw = n.alloc_var(N, H, W, ndf * mult, true);
   Var act = n.alloc_var(N, H, W, ndf * mult, true);
-  n.conv("model." + std::to_string(idx), a, raw, CK_K4S1, ndf * prev, ndf * mult, true, ACT_NONE);   // :124-128
-  n.norm_act(raw, act, true, ACT_LRELU, 0.f);
+  n.conv("model." + std::to_string(idx), a, raw, CK_K4S1, ndf * prev, ndf * mult, inner_bias, ACT_NONE);   // :124-128
+  patchgan_norm_act(n, norm, "model." + std::to_string(idx), raw, act);
   n.taps["d" + std::to_string(n_layers)] = act;
   idx += 3;
   H -= 1; W -= 1;
@@ -167,7 +181,8 @@ static void gan_loss_op(Stream& s, int mode, const TView& pred, float label, boo
 // the D input buffer orders it [cloth(19)+0 | body(3)+0] so the generator's tanh output and
 // the CE logits live in an aligned 20-channel slice.  Dx holds 2B images: [0,B) conditioned
 // fakes, [B,2B) conditioned targets -- the two D passes of backward_D run as one 2B batch
-// (InstanceNorm is per-sample, so batching is exact).
+// (InstanceNorm is per-sample, so batching is exact; under --norm batch the 2B net runs its BatchNorm sites with groups = 2: separate
+// statistics and one running update per half, fake half first, as the reference's two calls).
 // ---------------------------------------------------------------------------------------
 // First-layer buffers on the ring kernel (round 4).  The convs that read network inputs (cloth_down1: 19 -> 64, PatchGAN model.0:
 // 22 -> 64) ran on the register-staged f32-MFMA kernels because the LDS-DMA ring kernels walk the channels of a tap in 16-channel
@@ -221,17 +236,19 @@ class WarpModel final : public Model {
       std::vector<int32_t> cimap(CdB, -1);
       for (int i = 0; i < Cc; ++i) cimap[i] = Cb + i;     // cloth channels follow the body channels (warp_model.py:115)
       for (int i = 0; i < Cb; ++i) cimap[Ccp + i] = i;
-      d_cimap_ = cimap; d_layers_ = c.patchgan_layers;
+      d_cimap_ = cimap; d_layers_ = c.patchgan_layers; d_norm_ = c.patchgan_norm;
+      if (d_norm_ == 1 && !is_device_build())
+        throw Error(1, "WarpModel: --norm batch: BatchNorm is not implemented on the host simulator (HIP kernel only)");
       D2 = std::make_unique<Net>(c, arenaD);
       D2->keep_wino_inputs = true;
       D2->set_external_slot(Dx.vbase, slot_dx);
-      pred2 = build_patchgan(*D2, Dx, c.patchgan_layers, cimap);
+      pred2 = build_patchgan(*D2, Dx, c.patchgan_layers, cimap, 0, d_norm(2));
       if (!arenaD.frozen) arenaD.allocate(c);
       D2->finalize({pred2});
       // second instance over the first B images, bound to the same (now frozen) arena
       D1 = std::make_unique<Net>(c, arenaD);
       D1->set_external_slot(Dx.vbase, slot_dx);
-      pred1 = build_patchgan(*D1, Dx.batch(0, B), c.patchgan_layers, cimap, Ccp);      // d(fakes) only: the condition is data
+      pred1 = build_patchgan(*D1, Dx.batch(0, B), c.patchgan_layers, cimap, Ccp, d_norm(1));      // d(fakes) only: the condition is data
       // Cross-entropy term first (round 6).  d loss_G / d fakes = the PatchGAN pass's input gradient + the CE gradient; the CE term
       // needs neither network's update, so it is taken EARLY -- behind the discriminator's backward pass, where the main stream
       // otherwise waits 0.6 ms for the first layer's weight gradient and AdamW(D) on the second stream -- and writes the buffer; the
@@ -290,7 +307,8 @@ class WarpModel final : public Model {
   }
   TView output_view() override { return Dx.batch(0, B).v.slice(0, Ccp); }
   int output_channels() const override { return Cc; }
-  bool supports_gradient_penalty() const override { return d_layers_ >= 1; }      // (the reverse-over-reverse pass of gp.cpp walks the PatchGAN)
+  // (the reverse-over-reverse pass of gp.cpp walks the n-layer PatchGAN through InstanceNorm)
+  bool supports_gradient_penalty() const override { return d_layers_ >= 1 && d_norm_ == 0; }
   void forward(bool training, uint64_t seed) override {       // warp_model.py:106-107
     G->training = training; G->seed = seed;
     G->forward();

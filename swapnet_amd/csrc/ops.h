@@ -1,6 +1,6 @@
 // swapnet_amd -- device op launchers.  The engine (engine.cpp) is written against this
 // header only.  The product implementation is the set of HIP translation units in this
-// directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, losses.hip, optim.hip, gather.hip).
+// directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, batch_norm.hip, losses.hip, optim.hip, gather.hip).
 // tests/hostsim/hostsim_ops.cpp implements the same signatures with plain loops so that
 // the engine's graph / backward / packing logic can be checked in CI without a GPU; it is
 // never part of the shipped library.
@@ -8,6 +8,7 @@
 #include "common.h"
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 
 namespace swn {
 
@@ -56,6 +57,9 @@ void* stream_create(int device);          // selects the device, returns a new s
 void stream_destroy(void* handle);
 void device_check(int device);            // throws unless `device` is a usable HIP device; makes it current
 int is_device_build();                    // 1: HIP library, 0: CI host simulator
+// `warmup` untimed calls of `enqueue`, then `iters` timed ones back to back on s: ms_host[i] = HIP-event time of the i-th (tools/
+// bn_shapes.py through swn_op_norm_act_time).  Synchronises.  Device library only (the simulator has no device clock).
+void time_launches(Stream& s, int warmup, int iters, const std::function<void()>& enqueue, float* ms_host);
 void conv_force_naive(int on);            // route conv_fwd/conv_wgrad to the naive checkers (tests)
 // optional per-launch timing of the implicit-GEMM kernels (bench.py's roofline leg): when on,
 // every conv_fwd / conv_wgrad launch is bracketed by HIP events recorded on the launch stream.
@@ -287,6 +291,44 @@ void norm_act_bwd(Stream& s, const NormActBwdArgs& a);
 bool norm_act_bwd_emits_colsum(int HW, int C);
 // db[c] = sum_n partial[n][c]   (fixed order)
 void bias_grad_from_colsums(Stream& s, const double* partial, int N, int C, float* db);
+
+// ---- BatchNorm2d + activation (batch_norm.hip; modules/__init__.py:62-65: affine, running statistics, eps 1e-5, momentum 0.1) ----
+// The batch is `groups` (1 or 2) consecutive runs of N / groups images.  Training mode normalises every run with its own biased
+// statistics and updates the running buffers once per run, in run order, with the unbiased variance -- exactly what `groups`
+// separate calls on the runs would do (the discriminator's fake and real passes as one 2B batch).  Eval mode normalises with the
+// running buffers and changes nothing.  HIP kernels only: on the host simulator both launchers throw "not implemented".
+struct BatchNormArgs {
+  TView x;                    // raw conv output (dense)
+  TView y;                    // destination
+  const float* gamma = nullptr;      // [C]
+  const float* beta = nullptr;       // [C]
+  float* running_mean = nullptr;     // [C]; training: updated when given; eval: read
+  float* running_var = nullptr;
+  long long* num_batches_tracked = nullptr;   // optional device counter: += groups per training call
+  float* stats = nullptr;     // [groups][C][2] (mean, rstd); written in training mode
+  float* fold = nullptr;      // [groups][2][C] (scale = gamma * rstd, shift = beta - mean * scale); written, 16-byte aligned
+  int groups = 1;
+  int act = ACT_NONE;
+  int training = 1;
+  float* amax_out = nullptr;  // optional amax slot of y (see wino_input_transform)
+  // optional (training): the statistics' partial sums as the producing conv's epilogue left them (ConvFwdArgs::stat_partial)
+  const double* partial_in = nullptr;
+  int partial_chunks = 0;
+};
+void batch_norm_fwd(Stream& s, const BatchNormArgs& a);
+struct BatchNormBwdArgs {
+  TView dy;                   // grad wrt y
+  TView x;                    // raw conv output saved by forward
+  const float* stats = nullptr;      // as the training-mode forward left them
+  const float* fold = nullptr;
+  TView dx;                   // grad wrt x, overwritten
+  float* dgamma = nullptr;    // [C], overwritten; both NULL: the parameter gradients are skipped (dx is the same)
+  float* dbeta = nullptr;
+  int groups = 1;
+  int act = ACT_NONE;
+  float* amax_out = nullptr;  // optional amax slot of dx
+};
+void batch_norm_bwd(Stream& s, const BatchNormBwdArgs& a);
 
 // The keep/scale factor norm_act_fwd / norm_act_bwd apply at a dropout site, written out as an NCHW tensor
 // (N,C,H,W): element (n,c,h,w) = drop_scale(seed, ((n*H*W + h*W + w)*C + c), p) -- 0 or 1/(1-p).

@@ -147,6 +147,10 @@ class TextureModel final : public Model {
     ctx = &c; B = B_; H = H_; W = W_; is_train = train; num_roi = nroi;
     Cc = cloth_channels; Ccp = round_up(Cc, 4); RC = 3 * num_roi;
     if (Cc < 1 || Cc > 64) throw Error(1, "TextureModel: cloth_channels in [1,64]");
+    // --norm reaches the texture stage's pix2pix U-Net too (modules/swapnet_modules.py:176-187), which has no BatchNorm / no-norm form
+    if (c.patchgan_norm != 0)
+      throw Error(1, "TextureModel: a non-instance --norm is not implemented for the texture stage (its U-Net generator takes the same "
+                     "norm layer and exists under InstanceNorm only)");
     AllocScope mine(c, owned_allocs);
     G = std::make_unique<Net>(c, arenaG);
     G->keep_wino_inputs = train;

@@ -15,6 +15,7 @@ from . import _C
 NET_G, NET_D, NET_VGG = 0, 1, 2
 OPT_ADAMW, OPT_ADABOUND = 0, 1
 W_WEIGHT, W_GRAD, W_EXP_AVG, W_EXP_AVG_SQ = 0, 1, 2, 3
+NORM_KINDS = {"instance": 0, "batch": 1, "none": 2}       # --norm (swn_ctx_set_patchgan_norm)
 
 
 class Context:
@@ -148,7 +149,7 @@ class NativeModel:
     NHWC arenas.  Tensors cross the boundary as NCHW fp32, exactly as the reference holds them."""
 
     def __init__(self, ctx, kind, batch, height, width, is_train=True, dropout=0.5, num_roi=12, body_channels=3,
-                 cloth_channels=19, n_layers_D=3, share=None):
+                 cloth_channels=19, n_layers_D=3, share=None, norm="instance"):
         """share = another NativeModel of the same kind: the new model uses ITS parameter arenas (weights, gradients, Adam
         moments, step counters) and owns only activations -- the model of another batch size on the same training state
         (swn_model_create_shared)."""
@@ -156,6 +157,9 @@ class NativeModel:
         self.B, self.H, self.W, self.is_train = batch, height, width, is_train
         self.body_channels, self.cloth_channels = body_channels, cloth_channels
         self.n_layers_D = int(n_layers_D)
+        if norm not in NORM_KINDS:
+            raise NotImplementedError("normalization layer [%s] is not found" % norm)
+        self.norm = norm
         self.share = share
         if share is not None:
             if share.kind != kind:
@@ -163,13 +167,14 @@ class NativeModel:
             h = C.c_void_p()
             self.lib.call("swn_model_create_shared", share.handle, batch, height, width, C.byref(h))
             self.is_train, self.body_channels, self.cloth_channels = share.is_train, share.body_channels, share.cloth_channels
-            self.n_layers_D, self.out_channels = share.n_layers_D, share.out_channels
+            self.n_layers_D, self.out_channels, self.norm = share.n_layers_D, share.out_channels, share.norm
             self.handle = h
             self._keep = []
             return
         # a context-level option read at model construction (define_D's n_layers_D, base_gan.py:147): set it for this model,
         # whatever an earlier model on the same context asked for
         self.lib.call("swn_ctx_set_patchgan_layers", ctx.handle, self.n_layers_D)
+        self.lib.call("swn_ctx_set_patchgan_norm", ctx.handle, NORM_KINDS[norm])
         h = C.c_void_p()
         if kind == "warp":
             self.lib.call("swn_warp_model_create_ex", ctx.handle, batch, height, width, int(is_train),
@@ -196,6 +201,31 @@ class NativeModel:
             self.lib.call("swn_model_param_info", self.handle, net, i, buf, 256, C.byref(shape), C.byref(nd))
             out[buf.value.decode()] = tuple(shape[: nd.value])
         return out
+
+    def buffer_infos(self, net):
+        """state_dict() buffers of `net` (BatchNorm running statistics of the discriminator under norm="batch"):
+        name -> (shape, dtype)."""
+        n = C.c_int()
+        self.lib.call("swn_model_buffer_count", self.handle, net, C.byref(n))
+        out = OrderedDict()
+        buf = C.create_string_buffer(256)
+        for i in range(n.value):
+            numel, is64 = C.c_int(), C.c_int()
+            self.lib.call("swn_model_buffer_info", self.handle, net, i, buf, 256, C.byref(numel), C.byref(is64))
+            out[buf.value.decode()] = ((), torch.int64) if is64.value else ((numel.value,), torch.float32)
+        return out
+
+    def set_buffer(self, net, name, tensor, dtype):
+        t = tensor.detach().to(device=self.ctx.device, dtype=dtype).contiguous()
+        self._torch_done()
+        self.lib.call("swn_model_buffer_set", self.handle, net, name.encode(), _C.ptr(t))
+        self._sync_if_needed()
+
+    def get_buffer(self, net, name, shape, dtype):
+        t = torch.empty(shape, dtype=dtype, device=self.ctx.device)
+        self.lib.call("swn_model_buffer_get", self.handle, net, name.encode(), _C.ptr(t))
+        self._sync_if_needed()
+        return t
 
     def _dev(self, t):
         return t.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
@@ -228,8 +258,9 @@ class NativeModel:
 
     def load_state_dict(self, net, sd, which=W_WEIGHT, strict=True):
         infos = self.param_infos(net)
-        missing = [k for k in infos if k not in sd]
-        unexpected = [k for k in sd if k not in infos]
+        buffers = self.buffer_infos(net) if which == W_WEIGHT else {}       # (the optimizer's moments have no buffers)
+        missing = [k for k in list(infos) + list(buffers) if k not in sd]
+        unexpected = [k for k in sd if k not in infos and k not in buffers]
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict: missing {missing}, unexpected {unexpected}")
         for k, shape in infos.items():
@@ -237,6 +268,11 @@ class NativeModel:
                 if tuple(sd[k].shape) != tuple(shape):
                     raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(shape)}")
                 self.set_param(net, k, sd[k], which)
+        for k, (shape, dtype) in buffers.items():
+            if k in sd:
+                if tuple(sd[k].shape) != tuple(shape):
+                    raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(shape)}")
+                self.set_buffer(net, k, sd[k], dtype)
         self.ctx.sync()
 
     def state_dict(self, net, which=W_WEIGHT, to_cpu=False):
@@ -244,6 +280,10 @@ class NativeModel:
         for k, shape in self.param_infos(net).items():
             t = self.get_param(net, k, shape, which)
             out[k] = t.cpu() if to_cpu else t
+        if which == W_WEIGHT:
+            for k, (shape, dtype) in self.buffer_infos(net).items():
+                t = self.get_buffer(net, k, shape, dtype)
+                out[k] = t.cpu() if to_cpu else t
         self.ctx.sync()
         return out
 
@@ -342,9 +382,10 @@ class NativeModel:
         self.lib.call("swn_model_set_gp_random", self.handle, _C.ptr(a), _C.ptr(b))
         self._gp_keep = (a, b)
 
-    def discriminate(self, x):
+    def discriminate(self, x, training=True):
         """NLayerDiscriminator.forward on a conditioned input in the reference's channel order (B,C_D,H,W),
-        C_D = body + cloth channels (warp, 22 by default) / texture + cloth channels (texture)."""
+        C_D = body + cloth channels (warp, 22 by default) / texture + cloth channels (texture).  training: the module's mode
+        (only BatchNorm sites care: batch statistics + running update, or the running buffers)."""
         xd = x.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
         cd = self.cloth_channels + (self.body_channels if self.kind == "warp" else 3)
         if tuple(xd.shape) != (self.B, cd, self.H, self.W):
@@ -353,6 +394,7 @@ class NativeModel:
         shape = (self.B, 1, (self.H >> k) - 2, (self.W >> k) - 2) if k > 0 else (self.B, 1, self.H, self.W)     # 0: PixelDiscriminator
         pred = torch.empty(shape, dtype=torch.float32, device=self.ctx.device)
         self._torch_done()
+        self.lib.call("swn_model_set_discriminate_mode", self.handle, int(bool(training)))
         self.lib.call("swn_model_discriminate", self.handle, _C.ptr(xd), _C.ptr(pred))
         self.ctx.sync()
         return pred

@@ -63,6 +63,21 @@ class BaseGAN(BaseModel, ABC):
             self.backend.n_layers_D = int(opt.n_layers_D)
         elif self.is_train and getattr(opt, "discriminator", "basic") == "pixel":
             self.backend.n_layers_D = 0             # --discriminator pixel (base_gan.py:61-65): the 1x1 PixelDiscriminator
+        norm = getattr(opt, "norm", "instance")
+        if self.is_train and norm != "instance":
+            # --norm reaches the discriminator (modules/discriminators.py:77) and the texture stage's U-Net generator
+            # (modules/swapnet_modules.py:176-187); the warp generator hard-codes InstanceNorm.  So the warp stage is complete
+            # with a BatchNorm / no-norm PatchGAN; the texture stage would need the same for its generator.
+            modules.get_norm_layer(norm)            # unknown names fail like the reference
+            if self.KIND != "warp":
+                raise NotImplementedError("--norm %s is not implemented for the texture stage: the flag also selects the norm layer "
+                                          "of its pix2pix U-Net generator, which exists under instance norm only" % norm)
+            if opt.gan_mode in ("wgan-gp", "dragan-gp", "dragan-lp"):
+                raise NotImplementedError("gan mode %s with --norm %s: the native gradient penalty differentiates twice through "
+                                          "InstanceNorm only" % (opt.gan_mode, norm))
+            if norm == "batch" and not self.backend.ctx.lib.is_device:
+                raise NotImplementedError("--norm batch: BatchNorm is a HIP kernel only, the host simulator library has none")
+            self.backend.norm = norm                # the stage's native networks are built together, on first use
         self.net_generator = self.define_G()
         modules.init_weights(self.net_generator, opt.init_type, opt.init_gain)      # base_gan.py:141
         self.model_names = ["generator"]

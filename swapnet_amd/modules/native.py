@@ -22,6 +22,7 @@ class NativeBackend:
         self.body_channels, self.cloth_channels = body_channels, cloth_channels
         self.default_shape = tuple(default_shape)
         self.n_layers_D = 3         # define_D(..., n_layers_D): set by NLayerDiscriminator before the first model exists
+        self.norm = "instance"      # define_D(..., norm): the discriminator's norm layer, set the same way
         self.ctx = ctx or engine.default_context(device=device, lib=lib)
         self.models = {}
         self.cur = None
@@ -38,7 +39,7 @@ class NativeBackend:
             root = next(iter(self.models.values()), None)          # the first model owns the arenas, every later one shares them
             m = engine.NativeModel(self.ctx, self.kind, key[0], key[1], key[2], is_train=self.is_train,
                                    dropout=self.dropout, num_roi=self.num_roi, body_channels=self.body_channels,
-                                   cloth_channels=self.cloth_channels, n_layers_D=self.n_layers_D, share=root)
+                                   cloth_channels=self.cloth_channels, n_layers_D=self.n_layers_D, share=root, norm=self.norm)
             m.set_hyper(**self.hyper)
             for net, kw in self.optim.items():
                 m.set_optimizer(net, **kw)
