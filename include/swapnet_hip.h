@@ -39,7 +39,7 @@ typedef struct swn_ctx swn_ctx;
 typedef struct swn_model swn_model;
 
 int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lambda_gp; 4: swn_route_*, swn_model_step_captured, swn_model_create_shared;
-                                5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit */
+                                5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit; 8: swn_op_loss, swn_op_bias_grad */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -400,6 +400,19 @@ int swn_op_affine_gather(swn_ctx* ctx, const float* src, float* dst, int b, int 
  * grad_scale * d(loss)/d(pred). */
 int swn_op_gan_loss(swn_ctx* ctx, int gan_mode, const float* pred, int n, int c, int h, int w, float label,
                     int target_is_real, float grad_scale, float* loss_out, float* dpred);
+/* One loss kernel of ops.h on NCHW tensors (tests).  kind 0: ce_argmax_loss (a = logits, b = target, c <= 32), 1: l1_loss,
+ * 2: normed_mse_loss (c % 4 == 0, c <= 512), 3: gram_style_loss (n * c <= 1024; the only kind that reads n0 / nloc: nloc < 0 =
+ * the whole batch, otherwise the gradient is formed for samples [n0, n0 + nloc) and da holds nloc samples).
+ * The operands and the gradient live in buffers of c + pad_c channels ((c + pad_c) % 4 == 0) and the kernels get channel-slice
+ * views of them (pixel stride > C).  The pad channels of all three buffers hold the bit pattern 0x7f7f7f7f before the call;
+ * pad_out (optional, (n or nloc, pad_c, h, w)) receives the gradient buffer's pad channels after it.  accumulate != 0: the
+ * incoming contents of da are loaded first and the kernel adds to them.  loss_out = the plain mean (device float); da may be
+ * NULL (value only). */
+int swn_op_loss(swn_ctx* ctx, int kind, const float* a_nchw, const float* b_nchw, int n, int c, int h, int w, int pad_c,
+                float scale, int accumulate, int n0, int nloc, float* loss_out, float* da_nchw, float* pad_out);
+/* bias_grad (the column sums of dy over N*H*W) on a (c + pad_c)-channel buffer whose pads hold 0x7f7f7f7f; c, pad_c % 4 == 0;
+ * db = c device floats. */
+int swn_op_bias_grad(swn_ctx* ctx, const float* dy_nchw, int n, int c, int h, int w, int pad_c, float* db);
 /* [InstanceNorm] -> act -> nn.Dropout(p) in TRAINING mode as ONE op (UNetDown / ResidualBlock, modules/layers.py:
  * 18-23,133-136): y, the keep/scale mask it used (0 or 1/(1-p); may be NULL) and, when dy and dx are given, the
  * input gradient computed with the same mask.  NCHW fp32, C % 4 == 0. */

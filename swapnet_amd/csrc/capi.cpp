@@ -59,7 +59,7 @@ static int guard(F f) {
 
 extern "C" {
 
-int swn_abi_version(void) { return 7; }
+int swn_abi_version(void) { return 8; }
 const char* swn_last_error(void) { return g_err.c_str(); }
 int swn_is_device_build(void) { return is_device_build(); }
 
@@ -870,6 +870,59 @@ int swn_op_gan_loss(swn_ctx* ctx, int gan_mode, const float* pred, int n, int c,
     dev_copy(tmp.s, loss_out, lo, sizeof(float));
     if (dpred) nhwc_to_nchw(tmp.s, pv.g, dpred, 1);
     stream_sync(tmp.s);
+  });
+}
+// 0x7f7f7f7f = 3.39e38f in every pad channel: a kernel that sums a pad shows it at once, one that writes a pad changes the bits, and
+// 0 + sentinel keeps them (an accumulating kernel that adds zero into a pad leaves it as it was)
+static const int kPadSentinelByte = 0x7f;
+int swn_op_loss(swn_ctx* ctx, int kind, const float* a, const float* b, int n, int c, int h, int w, int pad_c, float scale,
+                int accumulate, int n0, int nloc, float* loss_out, float* da, float* pad_out) {
+  return guard([&] {
+    REQUIRE(ctx && a && b && loss_out, "NULL argument");
+    REQUIRE(kind >= 0 && kind <= 3, "bad loss kind");
+    REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && pad_c >= 0 && (c + pad_c) % 4 == 0, "bad shape (c + pad_c must be a multiple of 4)");
+    REQUIRE(!pad_out || (da && pad_c > 0), "pad_out needs a gradient and pad channels");
+    if (kind != 3 || nloc < 0) { n0 = 0; nloc = n; }
+    REQUIRE(n0 >= 0 && nloc >= 1 && n0 + nloc <= n, "bad n0 / nloc");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Stream& s = tmp.s;
+    const int cp = c + pad_c;
+    Var av = net.alloc_var(n, h, w, cp, false), bv = net.alloc_var(n, h, w, cp, false);
+    Var gv = net.alloc_var(nloc, h, w, cp, false);           // the gradient view: nloc samples (gram_style_loss), else the batch
+    for (const TView* t : {&av.v, &bv.v, &gv.v}) dev_memset(s, t->p, kPadSentinelByte, t->pixels() * t->cs * sizeof(float));
+    nchw_to_nhwc(s, a, n, c, h, w, av.v);
+    nchw_to_nhwc(s, b, n, c, h, w, bv.v);
+    if (da && accumulate) nchw_to_nhwc(s, da, nloc, c, h, w, gv.v);
+    // the logical channels as a slice of the wider buffer (cs > C); cross entropy takes the rounded-up slice, as the nets pass it
+    const int cv = kind == 0 ? round_up(c, 4) : c;
+    const TView va = av.v.slice(0, cv), vb = bv.v.slice(0, cv), vg = gv.v.slice(0, cv);
+    const TView* dp = da ? &vg : nullptr;
+    float* lo = static_cast<float*>(tmp.alloc(sizeof(float)));
+    if (kind == 0) ce_argmax_loss(s, va, vb, c, scale, lo, dp, accumulate);
+    else if (kind == 1) l1_loss(s, va, vb, c, scale, lo, dp, accumulate);
+    else if (kind == 2) normed_mse_loss(s, va, vb, scale, lo, dp, accumulate);
+    else gram_style_loss(s, va, vb, c, scale, lo, dp, accumulate, n0, nloc);
+    dev_copy(s, loss_out, lo, sizeof(float));
+    if (da) nhwc_to_nchw(s, gv.v, da, c);
+    if (pad_out) nhwc_to_nchw(s, gv.v.slice(c, pad_c), pad_out, pad_c);
+    stream_sync(s);
+  });
+}
+int swn_op_bias_grad(swn_ctx* ctx, const float* dy, int n, int c, int h, int w, int pad_c, float* db) {
+  return guard([&] {
+    REQUIRE(ctx && dy && db, "NULL argument");
+    REQUIRE(n > 0 && c > 0 && c % 4 == 0 && h > 0 && w > 0 && pad_c >= 0 && pad_c % 4 == 0, "bad shape (c and pad_c must be multiples of 4)");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Stream& s = tmp.s;
+    Var yv = net.alloc_var(n, h, w, c + pad_c, false);
+    dev_memset(s, yv.v.p, kPadSentinelByte, yv.v.pixels() * yv.v.cs * sizeof(float));
+    nchw_to_nhwc(s, dy, n, c, h, w, yv.v);
+    float* out = static_cast<float*>(tmp.alloc((size_t)c * sizeof(float)));
+    bias_grad(s, yv.v.slice(0, c), out);
+    dev_copy(s, db, out, (size_t)c * sizeof(float));
+    stream_sync(s);
   });
 }
 int swn_op_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const float* u, int n, int c, int h, int w, int act,

@@ -388,6 +388,12 @@ void labels_to_onehot(Stream& s, const int32_t* labels, const TView& y, int C); 
 
 // ---- losses: each writes the plain MEAN loss into *loss_out (device float) and, if a grad
 // view is given, scale * d(mean loss)/dx into it (scale carries lambda and the 0.5 of loss_D).
+// Views and pad channels (tests/test_loss_ops.py asserts every line of this): the kernels take channel-slice views (cs >= C) and
+// honour `accumulate` (dx += ..., else dx = ...).  They never read or write a channel at or above round_up(C, 4).  Channels in
+// [C, round_up(C, 4)): ce_argmax_loss moves whole float4 groups -- it reads them (and ignores what it read) and WRITES ZEROS
+// into those channels of dlogits (adds zero to them when it accumulates); l1_loss, gram_style_loss and the GAN losses (channel
+// 0 of the map only) touch the C logical channels alone; normed_mse_loss and bias_grad require C % 4 == 0.
+// All sums are fp64 partials of fp32 terms combined in a fixed order: two runs give bit-equal results.
 // BCEWithLogits(pred, label) mean over N*H*W of channel 0;  dpred = scale*(sigmoid-t)/numel
 // label_dev (optional): the label is read from device memory instead (captured training step)
 void bce_logits_loss(Stream& s, const TView& pred, float label, float scale, float* loss_out,
@@ -400,10 +406,14 @@ void ce_argmax_loss(Stream& s, const TView& logits, const TView& target, int C, 
                     float* loss_out, const TView* dlogits, int accumulate);
 void l1_loss(Stream& s, const TView& a, const TView& b, int C, float scale, float* loss_out,
              const TView* da, int accumulate);
-// content term of PerceptualLoss for one VGG slice: MSE of channel-L2-normalised features
+// content term of PerceptualLoss for one VGG slice: MSE of channel-L2-normalised features, y = x / (|x| + 1e-8) per pixel;
+// C % 4 == 0, C <= 512.  df = g / (s + eps) - f (f.g) / (s (s + eps)^2), s = |f|, g = 2 scale (y_f - y_t) / numel.
+// CONVENTION at a pixel with s == 0 (all-zero features, normal behind a ReLU): the second term is dropped, df = g / eps =
+// -2 scale y_t / (numel * 1e-8), finite.  The reference program's autograd gives NaN there (sqrt'(0) * 0); the loss value agrees.
 void normed_mse_loss(Stream& s, const TView& f, const TView& t, float scale, float* loss_out,
                      const TView* df, int accumulate);
-// style term: scale * MSE(Gram(a), Gram(b)), Gram over (N*C) x (H*W) of the raw images
+// style term: scale * MSE(Gram(a), Gram(b)), Gram over (N*C) x (H*W) of the raw images; N*C <= 1024.  Gram entries are fp32 fmaf
+// chains (64 pixels long when N*C <= 128 and the whole batch is differentiated, up to 1024 otherwise) added in fp64.
 // Under data parallelism a, b are the GLOBAL batches (all ranks' images, gathered by the host) and the gradient is
 // produced for the nloc samples starting at n0 only (da: a view of those samples); n0 = 0, nloc < 0: whole batch.
 void gram_style_loss(Stream& s, const TView& a, const TView& b, int C, float scale, float* loss_out,

@@ -519,6 +519,39 @@ def op_gan_loss(ctx, pred, gan_mode, label, target_is_real, grad_scale=1.0, want
     return loss, (d.reshape(shape) if d is not None else None)
 
 
+LOSS_CE, LOSS_L1, LOSS_NORMED_MSE, LOSS_GRAM = 0, 1, 2, 3
+PAD_SENTINEL = 0x7F7F7F7F           # what swn_op_loss / swn_op_bias_grad put into every pad channel before the call
+
+
+def op_loss(ctx, kind, a, b, pad_c=0, scale=1.0, accumulate=False, n0=0, nloc=-1, grad=None, want_grad=True, want_pad=True):
+    """One loss kernel through swn_op_loss on (N,C,H,W) operands held in C + pad_c channel buffers.  `grad`: the incoming gradient
+    (accumulate; nloc samples when nloc >= 0).  Returns (loss[1], da or None, the gradient buffer's pad channels or None)."""
+    a = a.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
+    b = b.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
+    n, c, h, w = a.shape
+    ng = n if nloc < 0 else nloc
+    loss = torch.empty(1, dtype=torch.float32, device=ctx.device)
+    d = pad = None
+    if want_grad:
+        d = (grad.detach().to(device=ctx.device, dtype=torch.float32).clone().contiguous() if accumulate
+             else torch.empty((ng, c, h, w), dtype=torch.float32, device=ctx.device))
+        assert tuple(d.shape) == (ng, c, h, w)
+        if want_pad and pad_c > 0:
+            pad = torch.empty((ng, pad_c, h, w), dtype=torch.float32, device=ctx.device)
+    ctx.lib.call("swn_op_loss", ctx.handle, int(kind), _C.ptr(a), _C.ptr(b), n, c, h, w, int(pad_c), C.c_float(scale),
+                 int(bool(accumulate)), int(n0), int(nloc), _C.ptr(loss), _C.ptr(d), _C.ptr(pad))
+    return loss, d, pad
+
+
+def op_bias_grad(ctx, dy, pad_c=0):
+    """bias_grad (column sums over N*H*W) through swn_op_bias_grad; dy (N,C,H,W) held in a C + pad_c channel buffer."""
+    d = dy.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
+    n, c, h, w = d.shape
+    db = torch.empty(c, dtype=torch.float32, device=ctx.device)
+    ctx.lib.call("swn_op_bias_grad", ctx.handle, _C.ptr(d), n, c, h, w, int(pad_c), _C.ptr(db))
+    return db
+
+
 def op_norm_act_bwd2(ctx, x, gy, u, act=1):
     """(uy, ax) of swn_op_norm_act_bwd2: the second-order step through act(InstanceNorm(x))."""
     d = [t.to(device=ctx.device, dtype=torch.float32).contiguous() for t in (x, gy, u)]

@@ -1129,15 +1129,17 @@ void lsgan_loss(Stream&, const TView& p, float l, float s, float* o, const TView
 void wgan_loss(Stream&, const TView& p, float l, float s, float* o, const TView* d) { gan(p, l, s, o, d, 2); }
 
 void ce_argmax_loss(Stream&, const TView& lg, const TView& tg, int C, float scale, float* out, const TView* dl, int accumulate) {
+  if (C > 32) throw Error(1, "ce_argmax_loss: needs C <= 32 and 16-byte aligned views");
   const size_t P = lg.pixels(); double acc = 0;
   for (size_t e = 0; e < P; ++e) {
     const float* lp = lg.p + e * lg.cs; const float* tp = tg.p + e * tg.cs;
     const int label = amax(tp, C);
     float lmax = lp[0]; for (int c = 1; c < C; ++c) lmax = std::fmax(lmax, lp[c]);
     float se = 0; for (int c = 0; c < C; ++c) se += std::exp(lp[c] - lmax);
-    acc += (lmax + std::log(se)) - lp[label];
+    acc += std::log(se) - (lp[label] - lmax);        // as ce_kernel: no cancellation against a large lmax
     if (dl) { float* dp = dl->p + e * dl->cs;
-      for (int c = 0; c < C; ++c) { float g = (std::exp(lp[c] - lmax) / se - (c == label)) * scale / (float)P; dp[c] = accumulate ? dp[c] + g : g; } }
+      for (int c = 0; c < C; ++c) { float g = (std::exp(lp[c] - lmax) / se - (c == label)) * scale / (float)P; dp[c] = accumulate ? dp[c] + g : g; }
+      if (!accumulate) for (int c = C; c < round_up(C, 4); ++c) dp[c] = 0.f; }        // whole float4 groups, as ce_kernel (ops.h)
   }
   *out = (float)(acc / P);
 }
@@ -1150,15 +1152,18 @@ void l1_loss(Stream&, const TView& a, const TView& b, int C, float scale, float*
   *out = (float)(acc / n);
 }
 void normed_mse_loss(Stream&, const TView& f, const TView& t, float scale, float* out, const TView* df, int accumulate) {
+  if (f.C % 4 || f.C > 512 || t.C != f.C) throw Error(1, "normed_mse_loss: C must be a multiple of 4, <= 512");
   const size_t P = f.pixels(); const int C = f.C; double acc = 0; const float numel = (float)(P * C);
   std::vector<float> g(C);
   for (size_t e = 0; e < P; ++e) {
     const float* fp = f.p + e * f.cs; const float* tp = t.p + e * t.cs;
-    float sf = 0, st = 0; for (int c = 0; c < C; ++c) { sf += fp[c] * fp[c]; st += tp[c] * tp[c]; }
-    sf = std::sqrt(sf); st = std::sqrt(st);
+    // (the kernel sums 8 values per lane and folds the wave as a tree: a C-long sequential fp32 sum would be less accurate than it)
+    double sfd = 0, std_ = 0; for (int c = 0; c < C; ++c) { sfd += (double)fp[c] * fp[c]; std_ += (double)tp[c] * tp[c]; }
+    float sf = std::sqrt((float)sfd), st = std::sqrt((float)std_);
     const float inf = 1.f / (sf + 1e-8f), intt = 1.f / (st + 1e-8f);
-    float dot = 0;
-    for (int c = 0; c < C; ++c) { g[c] = fp[c] * inf - tp[c] * intt; acc += (double)g[c] * g[c]; dot += g[c] * fp[c]; }
+    double dotd = 0;
+    for (int c = 0; c < C; ++c) { g[c] = fp[c] * inf - tp[c] * intt; acc += (double)g[c] * g[c]; dotd += (double)g[c] * fp[c]; }
+    const float dot = (float)dotd;
     if (df) { const float k2 = sf > 0 ? dot * inf * inf / sf : 0.f; float* dp = df->p + e * df->cs;
       for (int c = 0; c < C; ++c) { float o = (g[c] * inf - fp[c] * k2) * 2.f * scale / numel; dp[c] = accumulate ? dp[c] + o : o; } }
   }
@@ -1168,6 +1173,7 @@ void gram_style_loss(Stream&, const TView& a, const TView& b, int C, float scale
                      int n0, int nloc) {
   const int R = a.N * C, HW = a.H * a.W;
   if (nloc < 0) { n0 = 0; nloc = a.N; }
+  if (R > 1024) throw Error(1, "gram_style_loss: N*C > 1024 unsupported");
   std::vector<double> Ga((size_t)R * R, 0.0), Gb((size_t)R * R, 0.0);
   auto val = [&](const TView& v, int r, int p) { return v.p[((size_t)(r / C) * HW + p) * v.cs + (r % C)]; };
   for (int r1 = 0; r1 < R; ++r1) for (int r2 = 0; r2 < R; ++r2) { double s1 = 0, s2 = 0;
