@@ -189,6 +189,16 @@ int swn_model_set_input(swn_model* m, int slot, const float* dev_nchw, int n, in
  * one-hot expansion (label 0 -> all-zero vector) happens on the device: 1/19 of the H2D bytes of
  * set_input(one_hot).  Bit-identical to to_onehot_tensor + set_input. */
 int swn_model_set_input_labels(swn_model* m, int slot, const int32_t* dev_labels, int n, int h, int w);
+/* Texture models: all four slots of a step from the COMPACT batch, one device launch (swn_op_texture_batch below has the
+ * arithmetic): img (B,hs,ws,3) uint8 = the samples after tf.resize(img, load_size), labels (B,hl,wl) uint8 = the cloth label maps as
+ * stored, rois_raw (B,R,4) float32 = the ROI table's rows, sample (B,5) float32 = {vflip, hflip, roi_scale, cy, cx} per sample --
+ * all device pointers; mean3 / std3 = the texture statistics, HOST floats.  The crop window is the model's H x W at (x_min, y_min)
+ * of the hs x ws source.  Writes slot 0 (input_textures), 1 (rois), 2 (cloths) and, when training, 3 (target_textures),
+ * bit-identically to swn_model_set_input on the tensors TextureDataset.__getitem__ builds (datasets/texture_dataset.py:87-160).
+ * An inference model has no target: nothing of it is written. */
+int swn_model_set_input_texture_batch(swn_model* m, const uint8_t* img, int b, int hs, int ws, const uint8_t* labels, int hl, int wl,
+                                      const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3,
+                                      int x_min, int y_min);
 /* slot 0: self.fakes (B,19,H,W) warp / (B,3,H,W) texture */
 int swn_model_get_output(swn_model* m, int slot, float* dev_nchw);
 /* named intermediate activation (debug / per-level parity tests), copied out as NCHW */
@@ -394,6 +404,23 @@ int swn_op_norm_act_time(swn_ctx* ctx, int kind, int what, const float* x, const
  * NEAREST sampling.  swapnet_amd/datasets/gpu_augment.py draws the parameters like torchvision's transforms do. */
 int swn_op_affine_gather(swn_ctx* ctx, const float* src, float* dst, int b, int c, int h, int w, const double* maps,
                          int nmaps);
+/* TextureDataset.__getitem__ (datasets/texture_dataset.py:87-160, datasets/data_utils.py:169-295) for a whole batch as ONE device
+ * launch, from the compact form (arguments as swn_model_set_input_texture_batch; h x w = the crop window at (x_min, y_min)).
+ * With (y, x) a pixel of the window, everything in fp32, one correctly rounded operation per step:
+ *   tgt_nchw (B,3,h,w)  = (float(img[y_min + y, x_min + x]) / 255 - mean) / std                       to_tensor, Normalize, crop
+ *   in_nchw  (B,3,h,w)  = the same of the flipped image: rows mirrored if vflip, then columns if hflip   random_image_roi_flip
+ *   cloths_nchw (B,cloth_channels,h,w) = one-hot (label 0: all zero) of labels[min(int(floorf((y_min + y) * (float(hl) / hs))),
+ *                         hl - 1)], likewise in x                       to_onehot_tensor, F.interpolate(size = (hs, ws)), crop
+ *   rois_out (B,R,4)    = rint(rois_raw * roi_scale); vflip: (y1, y2) <- (-(y2 - cy) + cy, -(y1 - cy) + cy); hflip: the same in x
+ *                         with cx; crop: clamp(x, x_min, x_min + w - 1) - x_min, likewise y.  A window that is the whole source
+ *                         is the reference's "no crop_bounds": the ROIs are then NOT clamped (crop_rois(rois, None)).
+ * cy, cx = int(H0 / 2), int(W0 / 2) of the image BEFORE the resize -- the reference flips the ROIs about the original centre.
+ * The resized image is flipped here where the reference flips and resizes a second time; Pillow's resize commutes with both flips
+ * bit for bit (tests/test_texture_batch.py).  rois_out must be 16-byte aligned. */
+int swn_op_texture_batch(swn_ctx* ctx, const uint8_t* img, int b, int hs, int ws, const uint8_t* labels, int hl, int wl,
+                         const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3, int x_min,
+                         int y_min, int h, int w, int cloth_channels, float* in_nchw, float* tgt_nchw, float* cloths_nchw,
+                         float* rois_out);
 /* GANLoss(gan_mode)(prediction, target_is_real) (modules/loss.py:110-130) with the target scalar already drawn
  * (`label`; the smooth-label draw stays host-side like in the reference, loss.py:65-108): mean BCE-with-logits /
  * MSE / +-mean over ALL elements of pred (N,C,H,W).  loss_out = device float; dpred (optional, same shape) receives

@@ -367,6 +367,14 @@ int swn_model_set_input(swn_model* m, int slot, const float* src, int n, int c, 
 int swn_model_set_input_labels(swn_model* m, int slot, const int32_t* lab, int n, int h, int w) {
   return guard([&] { REQUIRE(m && lab, "NULL argument"); m->m->set_input_labels(slot, lab, n, h, w); });
 }
+int swn_model_set_input_texture_batch(swn_model* m, const uint8_t* img, int b, int hs, int ws, const uint8_t* labels, int hl, int wl,
+                                      const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3,
+                                      int x_min, int y_min) {
+  return guard([&] {
+    REQUIRE(m && img && labels && rois_raw && sample && mean3 && std3, "NULL argument");
+    m->m->set_input_texture_batch(img, b, hs, ws, labels, hl, wl, rois_raw, r, sample, mean3, std3, x_min, y_min);
+  });
+}
 int swn_model_get_output(swn_model* m, int slot, float* dst) {
   return guard([&] { REQUIRE(m && dst, "NULL argument"); m->m->get_output(slot, dst); });
 }
@@ -850,6 +858,32 @@ int swn_op_affine_gather(swn_ctx* ctx, const float* src, float* dst, int b, int 
     REQUIRE(ctx && src && dst && maps, "NULL argument");
     REQUIRE(src != dst, "affine_gather is out of place");
     affine_gather(ctx->c->s, src, dst, b, c, h, w, maps, nmaps);
+  });
+}
+int swn_op_texture_batch(swn_ctx* ctx, const uint8_t* img, int b, int hs, int ws, const uint8_t* labels, int hl, int wl,
+                         const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3, int x_min,
+                         int y_min, int h, int w, int cloth_channels, float* in_nchw, float* tgt_nchw, float* cloths_nchw,
+                         float* rois_out) {
+  return guard([&] {
+    REQUIRE(ctx && img && labels && rois_raw && sample && mean3 && std3 && in_nchw && tgt_nchw && cloths_nchw && rois_out, "NULL argument");
+    REQUIRE(b > 0 && h > 0 && w > 0, "texture_batch: empty sizes");
+    REQUIRE(cloth_channels >= 1 && cloth_channels <= 64, "texture_batch: cloth channels in [1,64]");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    // one buffer [input texel | target texel | one-hot], so that every destination is a channel slice like the model's
+    const int cp = round_up(cloth_channels, 4);
+    Var t = net.alloc_var(b, h, w, 8 + cp, false);
+    TextureBatchArgs a;
+    a.img = img; a.Hs = hs; a.Ws = ws; a.labels = labels; a.Hl = hl; a.Wl = wl; a.rois_raw = rois_raw; a.R = r; a.sample = sample;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.std[c] = std3[c]; }
+    a.x_min = x_min; a.y_min = y_min; a.C = cloth_channels;
+    a.in_tex = t.v.slice(0, 4); a.tgt_tex = t.v.slice(4, 4); a.cloth[0] = t.v.slice(8, cp); a.ncloth = 1;
+    a.rois_out = rois_out;
+    texture_batch(tmp.s, a);
+    nhwc_to_nchw(tmp.s, a.in_tex, in_nchw, 3);
+    nhwc_to_nchw(tmp.s, a.tgt_tex, tgt_nchw, 3);
+    nhwc_to_nchw(tmp.s, a.cloth[0], cloths_nchw, cloth_channels);
+    stream_sync(tmp.s);
   });
 }
 int swn_op_gan_loss(swn_ctx* ctx, int gan_mode, const float* pred, int n, int c, int h, int w, float label,

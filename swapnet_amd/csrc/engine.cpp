@@ -1580,6 +1580,10 @@ void Model::run_gradient_penalty(const TView& real, const TView& fake) {
 void Model::set_style_context(const float*, const float*, int, int) {
   throw Error(1, "set_style_context: only the texture model has a style term");
 }
+void Model::set_input_texture_batch(const uint8_t*, int, int, int, const uint8_t*, int, int, const float*, int, const float*, const float*,
+                                    const float*, int, int) {
+  throw Error(1, "set_input_texture_batch: only the texture model takes a texture batch");
+}
 void Model::perceptual(const float*, const float*, int, float*, float, float, float*) {
   throw Error(1, "perceptual: only the texture model carries the VGG16 network (not implemented for this model)");
 }
@@ -1728,6 +1732,57 @@ __attribute__((weak)) void batch_norm_bwd(Stream&, const BatchNormBwdArgs&) {
 }
 __attribute__((weak)) void time_launches(Stream&, int, int, const std::function<void()>&, float*) {
   throw Error(1, "time_launches: device timing is not implemented on the host simulator");
+}
+
+// Host form of the texture batch hand-over (ops.h texture_batch).  Weak like the fallbacks above, but a real implementation: the
+// same expressions in the same order as texture_batch.hip, so the host simulator hands batches over too.
+__attribute__((weak)) void texture_batch(Stream&, const TextureBatchArgs& a) {
+  texture_batch_check(a);
+  const int B = a.in_tex.N, H = a.in_tex.H, W = a.in_tex.W, Cp = round_up(a.C, 4);
+  const bool clamp_rois = !(a.x_min == 0 && a.y_min == 0 && H == a.Hs && W == a.Ws);
+  const float lscale_y = (float)a.Hl / (float)a.Hs, lscale_x = (float)a.Wl / (float)a.Ws;
+  auto texel = [&](const uint8_t* px, float* dst) {
+    for (int c = 0; c < 3; ++c) {
+      volatile float t = (float)px[c] / 255.f;           // (volatile: one rounded fp32 operation per step, whatever the compiler's contraction rules)
+      volatile float d = t - a.mean[c];
+      dst[c] = d / a.std[c];
+    }
+    dst[3] = 0.f;
+  };
+  for (int b = 0; b < B; ++b) {
+    const float* sp = a.sample + (size_t)b * 5;
+    const bool vf = sp[0] != 0.f, hf = sp[1] != 0.f;
+    const uint8_t* im = a.img + (size_t)b * a.Hs * a.Ws * 3;
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const size_t pix = ((size_t)b * H + y) * W + x;
+        const int sy = a.y_min + y, sx = a.x_min + x;
+        const int fy = vf ? a.Hs - 1 - sy : sy, fx = hf ? a.Ws - 1 - sx : sx;
+        texel(im + ((size_t)fy * a.Ws + fx) * 3, a.in_tex.p + pix * a.in_tex.cs);
+        if (a.tgt_tex.p) texel(im + ((size_t)sy * a.Ws + sx) * 3, a.tgt_tex.p + pix * a.tgt_tex.cs);
+        const int ly = std::min((int)floorf((float)sy * lscale_y), a.Hl - 1), lx = std::min((int)floorf((float)sx * lscale_x), a.Wl - 1);
+        const int l = a.labels[((size_t)b * a.Hl + ly) * a.Wl + lx];
+        for (int k = 0; k < a.ncloth; ++k) {
+          float* dst = a.cloth[k].p + pix * a.cloth[k].cs;
+          for (int c = 0; c < Cp; ++c) dst[c] = (c == l && l != 0 && l < a.C) ? 1.f : 0.f;
+        }
+      }
+    auto mirror = [](float v, float c) { volatile float d = v - c; return -d + c; };
+    auto crop1 = [](float v, float lo, float hi) { return std::fmin(std::fmax(v, lo), hi) - lo; };
+    for (int r = 0; r < a.R; ++r) {
+      const float* raw = a.rois_raw + ((size_t)b * a.R + r) * 4;
+      float* out = a.rois_out + ((size_t)b * a.R + r) * 4;
+      float v[4];
+      for (int j = 0; j < 4; ++j) { volatile float m = raw[j] * sp[2]; v[j] = rintf(m); }
+      if (vf) { const float lo = mirror(v[3], sp[3]), hi = mirror(v[1], sp[3]); v[1] = lo; v[3] = hi; }      // vertical first
+      if (hf) { const float lo = mirror(v[2], sp[4]), hi = mirror(v[0], sp[4]); v[0] = lo; v[2] = hi; }
+      if (clamp_rois) {
+        const float xl = (float)a.x_min, xh = (float)(a.x_min + W - 1), yl = (float)a.y_min, yh = (float)(a.y_min + H - 1);
+        v[0] = crop1(v[0], xl, xh); v[2] = crop1(v[2], xl, xh); v[1] = crop1(v[1], yl, yh); v[3] = crop1(v[3], yl, yh);
+      }
+      for (int j = 0; j < 4; ++j) out[j] = v[j];
+    }
+  }
 }
 
 }  // namespace swn

@@ -405,6 +405,11 @@ class Model {
   Hyper hyper;
   virtual void set_input(int slot, const float* dev_nchw, int N, int C, int Hh, int Ww) = 0;
   virtual void set_input_labels(int slot, const int32_t* dev_labels, int N, int Hh, int Ww) = 0;
+  // texture models: every input slot of a step from the compact batch in one launch (ops.h texture_batch); the crop window is the
+  // model's H x W at (x_min, y_min) of the Hs x Ws source
+  virtual void set_input_texture_batch(const uint8_t* img, int N, int Hs, int Ws, const uint8_t* labels, int Hl, int Wl,
+                                       const float* rois_raw, int R, const float* sample, const float mean[3], const float std_[3],
+                                       int x_min, int y_min);
   virtual void get_output(int slot, float* dev_nchw) = 0;
   virtual TView output_view() = 0;              // NHWC view of self.fakes (logical channels: cloth_channels warp / 3 texture)
   virtual int output_channels() const = 0;

@@ -1,6 +1,7 @@
 // swapnet_amd -- device op launchers.  The engine (engine.cpp) is written against this
 // header only.  The product implementation is the set of HIP translation units in this
-// directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, batch_norm.hip, losses.hip, optim.hip, gather.hip).
+// directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, batch_norm.hip, losses.hip, optim.hip, gather.hip,
+// texture_batch.hip).
 // tests/hostsim/hostsim_ops.cpp implements the same signatures with plain loops so that
 // the engine's graph / backward / packing logic can be checked in CI without a GPU; it is
 // never part of the shipped library.
@@ -385,6 +386,49 @@ void nhwc_to_nchw(Stream& s, const TView& src, float* dst, int C);
 void decode_labels(Stream& s, const TView& x, int C, uint8_t* rgb_nchw);            // util/decode_labels.py
 void argmax_labels(Stream& s, const TView& x, int C, int32_t* labels);              // data_utils.py:322
 void labels_to_onehot(Stream& s, const int32_t* labels, const TView& y, int C);     // data_utils.py:330-343
+
+// ---- texture batch hand-over (texture_batch.hip) ------------------------------------------------------------------------------
+// What TextureDataset.__getitem__ (datasets/texture_dataset.py:87-160, datasets/data_utils.py:169-295) computes per sample on the
+// host, for a whole batch in ONE launch, from the compact form: the resized uint8 HWC image, the uint8 label map, the raw ROI table
+// and five scalars per sample.  With (y, x) a pixel of the H x W crop window at (y_min, x_min) of the Hs x Ws source:
+//   tgt_tex[b,y,x,c] = (float(img[b, y_min + y, x_min + x, c]) / 255 - mean[c]) / std[c]                       (to_tensor, Normalize)
+//   in_tex          = the same of the flipped image: row Hs-1-. if vflip, then column Ws-1-. if hflip      (random_image_roi_flip)
+//   cloth[k][b,y,x,:] = one-hot of labels[b, min(int(floorf((y_min + y) * (float(Hl) / Hs))), Hl - 1), likewise for x]; label 0 and
+//                     labels >= C give the all-zero vector                      (to_onehot_tensor, F.interpolate nearest, then the crop)
+//   rois_out[b,r]   = v = rintf(rois_raw * roi_scale); vflip: (y1, y2) <- (-(y2 - cy) + cy, -(y1 - cy) + cy); hflip: the same on x
+//                     with cx; then clamp(x, x_min, x_min + W - 1) - x_min and likewise for y                (flip_rois_, crop_rois)
+// all in fp32, one correctly rounded operation per step, pad channels of every view written as zero.  The ROI clamp belongs to the
+// crop: a window that is the whole source (x_min = y_min = 0, H = Hs, W = Ws) is the reference's "no crop_bounds" and leaves the
+// ROIs unclamped, as its crop_rois(rois, None) does.  Every view must be 16-byte tileable (C % 4, cs % 4, aligned base).
+struct TextureBatchArgs {
+  const uint8_t* img = nullptr; int Hs = 0, Ws = 0;          // (B,Hs,Ws,3)
+  const uint8_t* labels = nullptr; int Hl = 0, Wl = 0;       // (B,Hl,Wl)
+  const float* rois_raw = nullptr; int R = 0;                // (B,R,4)
+  const float* sample = nullptr;                             // (B,5): vflip, hflip, roi_scale, cy, cx
+  float mean[3] = {0.f, 0.f, 0.f}, std[3] = {1.f, 1.f, 1.f}; int x_min = 0, y_min = 0; int C = 0;   // C = cloth channels
+  TView in_tex, tgt_tex;                                     // 4-channel NHWC views; tgt_tex may be empty (inference)
+  TView cloth[3]; int ncloth = 0;                            // up to three one-hot destinations, C padded to a multiple of 4
+  float* rois_out = nullptr;                                 // (B,R,4)
+};
+void texture_batch(Stream& s, const TextureBatchArgs& a);
+// the argument checks of every texture_batch implementation (the HIP launcher and the host loop of engine.cpp)
+inline void texture_batch_check(const TextureBatchArgs& a) {
+  auto tileable = [](const TView& v) { return v.p && v.C % 4 == 0 && v.cs % 4 == 0 && v.cs >= v.C && !((uintptr_t)v.p & 15); };
+  const TView& t = a.in_tex;
+  if (!a.img || !a.labels || !a.rois_raw || !a.sample || !a.rois_out) throw Error(1, "texture_batch: NULL argument");
+  if ((uintptr_t)a.rois_out & 15) throw Error(1, "texture_batch: rois_out not 16-byte aligned");
+  if (t.N < 1 || t.H < 1 || t.W < 1 || a.Hs < 1 || a.Ws < 1 || a.Hl < 1 || a.Wl < 1 || a.R < 1) throw Error(1, "texture_batch: empty sizes");
+  if (a.x_min < 0 || a.y_min < 0 || a.x_min > a.Ws - t.W || a.y_min > a.Hs - t.H)
+    throw Error(1, "texture_batch: crop window (" + std::to_string(a.x_min) + ", " + std::to_string(a.y_min) + ") + " + std::to_string(t.W) +
+                       " x " + std::to_string(t.H) + " lies outside the " + std::to_string(a.Ws) + " x " + std::to_string(a.Hs) + " source");
+  if (a.C < 1 || a.C > 64) throw Error(1, "texture_batch: cloth channels in [1,64]");
+  if (a.ncloth < 1 || a.ncloth > 3) throw Error(1, "texture_batch: one to three cloth destinations");
+  if (!tileable(t) || t.C != 4) throw Error(1, "texture_batch in_tex: view not a 16-byte tileable 4-channel view");
+  auto same = [&](const TView& v) { return v.N == t.N && v.H == t.H && v.W == t.W; };
+  if (a.tgt_tex.p && (!tileable(a.tgt_tex) || a.tgt_tex.C != 4 || !same(a.tgt_tex))) throw Error(1, "texture_batch tgt_tex: view mismatch");
+  for (int k = 0; k < a.ncloth; ++k)
+    if (!tileable(a.cloth[k]) || a.cloth[k].C != round_up(a.C, 4) || !same(a.cloth[k])) throw Error(1, "texture_batch cloth: view mismatch");
+}
 
 // ---- losses: each writes the plain MEAN loss into *loss_out (device float) and, if a grad
 // view is given, scale * d(mean loss)/dx into it (scale carries lambda and the 0.5 of loss_D).

@@ -294,6 +294,28 @@ class TextureModel final : public Model {
     labels_to_onehot(ctx->s, lab, Dx.batch(0, B).v.slice(4, Ccp), Cc);
     if (is_train) labels_to_onehot(ctx->s, lab, Dx.batch(B, B).v.slice(4, Ccp), Cc);
   }
+  // slots 0-3 from the compact batch, one launch (ops.h texture_batch) instead of the six of the calls above
+  void set_input_texture_batch(const uint8_t* img, int N, int Hs, int Ws, const uint8_t* labels, int Hl, int Wl, const float* rois_raw,
+                               int R, const float* sample, const float mean[3], const float std_[3], int x_min, int y_min) override {
+    if (N != B) throw Error(1, "set_input_texture_batch: shape mismatch with the model's batch");
+    if (R != num_roi) throw Error(1, "rois must be (B, num_roi, 4)");
+    vt_done_ = false;
+    TextureBatchArgs a;
+    a.img = img; a.Hs = Hs; a.Ws = Ws; a.labels = labels; a.Hl = Hl; a.Wl = Wl; a.rois_raw = rois_raw; a.R = R; a.sample = sample;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std_[c]; }
+    a.x_min = x_min; a.y_min = y_min; a.C = Cc;
+    a.in_tex = tex.v;
+    a.cloth[0] = unet_in.v.slice(RC, Ccp);
+    a.cloth[1] = Dx.batch(0, B).v.slice(4, Ccp);
+    a.ncloth = 2;
+    if (is_train) {
+      a.cloth[2] = Dx.batch(B, B).v.slice(4, Ccp);
+      a.ncloth = 3;
+      a.tgt_tex = Dx.batch(B, B).v.slice(0, 4);
+    }
+    a.rois_out = rois;
+    texture_batch(ctx->s, a);
+  }
   void get_output(int slot, float* dst) override {
     if (slot != 0) throw Error(1, "get_output: unknown slot");
     nhwc_to_nchw(ctx->s, Dx.batch(0, B).v.slice(0, 4), dst, 3);

@@ -331,6 +331,30 @@ class NativeModel:
         self.ctx.consumed(token)
         self._keep_labels = t
 
+    def set_input_texture_batch(self, batch):
+        """Texture model: every input slot from the compact batch dict of datasets.gpu_texture_batch.GpuTextureBatch.collate
+        (uint8 images and label maps, raw ROIs, five scalars per sample) in one device launch."""
+        specs = (("textures_u8", torch.uint8), ("cloth_labels_u8", torch.uint8), ("rois_raw", torch.float32), ("sample_params", torch.float32))
+        dev, tokens = [], []
+        for name, dtype in specs:
+            t, token = self.ctx.upload(torch.as_tensor(batch[name]), dtype, key=(id(self), "tb", name))
+            dev.append(t); tokens.append(token)
+        img, lab, rois, sample = dev
+        if img.dim() != 4 or img.shape[3] != 3 or lab.dim() != 3 or rois.dim() != 3 or rois.shape[2] != 4 or tuple(sample.shape) != (img.shape[0], 5):
+            raise ValueError("texture batch: textures_u8 (B,Hs,Ws,3), cloth_labels_u8 (B,Hl,Wl), rois_raw (B,R,4), sample_params (B,5)")
+        if lab.shape[0] != img.shape[0] or rois.shape[0] != img.shape[0]:
+            raise ValueError("texture batch: the batch sizes of its tensors differ")
+        mean, std = batch["norm_stats"]
+        x_min, y_min = batch["crop"][:2]
+        self._torch_done()
+        self.lib.call("swn_model_set_input_texture_batch", self.handle, _C.ptr(img), img.shape[0], img.shape[1], img.shape[2],
+                      _C.ptr(lab), lab.shape[1], lab.shape[2], _C.ptr(rois), rois.shape[1], _C.ptr(sample),
+                      (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(x_min), int(y_min))
+        self._sync_if_needed()
+        for token in tokens:
+            self.ctx.consumed(token)
+        self._keep = dev
+
     def forward(self, training=False, seed=0):
         self.lib.call("swn_model_forward", self.handle, int(training), C.c_uint64(seed))
 
@@ -550,6 +574,31 @@ def op_bias_grad(ctx, dy, pad_c=0):
     db = torch.empty(c, dtype=torch.float32, device=ctx.device)
     ctx.lib.call("swn_op_bias_grad", ctx.handle, _C.ptr(d), n, c, h, w, int(pad_c), _C.ptr(db))
     return db
+
+
+def op_texture_batch(ctx, textures_u8, labels_u8, rois_raw, sample_params, mean, std, x_min, y_min, height, width, cloth_channels=19):
+    """TextureDataset.__getitem__ for a batch through swn_op_texture_batch: (input_textures, target_textures, cloths, rois) on the
+    context's device, NCHW float32 / (B,R,4), from uint8 HWC images (B,Hs,Ws,3), uint8 label maps (B,Hl,Wl), raw ROIs (B,R,4) and
+    the (B,5) per-sample scalars {vflip, hflip, roi_scale, cy, cx}."""
+    img = torch.as_tensor(textures_u8).to(device=ctx.device, dtype=torch.uint8).contiguous()
+    lab = torch.as_tensor(labels_u8).to(device=ctx.device, dtype=torch.uint8).contiguous()
+    rois = torch.as_tensor(rois_raw).to(device=ctx.device, dtype=torch.float32).contiguous()
+    sample = torch.as_tensor(sample_params).to(device=ctx.device, dtype=torch.float32).contiguous()
+    if img.dim() != 4 or img.shape[3] != 3 or lab.dim() != 3 or rois.dim() != 3 or rois.shape[2] != 4:
+        raise ValueError("texture batch: textures_u8 (B,Hs,Ws,3), labels_u8 (B,Hl,Wl), rois_raw (B,R,4)")
+    b = img.shape[0]
+    if lab.shape[0] != b or rois.shape[0] != b or tuple(sample.shape) != (b, 5):
+        raise ValueError("texture batch: labels, ROIs and sample_params (B,5) must share the images' batch size")
+    inp = torch.empty((b, 3, height, width), dtype=torch.float32, device=ctx.device)
+    tgt = torch.empty_like(inp)
+    cloths = torch.empty((b, cloth_channels, height, width), dtype=torch.float32, device=ctx.device)
+    out = torch.empty(tuple(rois.shape), dtype=torch.float32, device=ctx.device)
+    if ctx.owns_stream:                     # (the uploads above ran on torch's stream)
+        torch.cuda.current_stream(ctx.device).synchronize()
+    ctx.lib.call("swn_op_texture_batch", ctx.handle, _C.ptr(img), b, img.shape[1], img.shape[2], _C.ptr(lab), lab.shape[1], lab.shape[2],
+                 _C.ptr(rois), rois.shape[1], _C.ptr(sample), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(x_min), int(y_min),
+                 int(height), int(width), int(cloth_channels), _C.ptr(inp), _C.ptr(tgt), _C.ptr(cloths), _C.ptr(out))
+    return inp, tgt, cloths, out
 
 
 def op_norm_act_bwd2(ctx, x, gy, u, act=1):

@@ -117,8 +117,40 @@ class TextureModel(BaseGAN):
             raise NotImplementedError("netG unet_128 (plain pix2pix baseline) is not implemented natively")
         raise ValueError("Cannot find implementation for " + netG)
 
+    # self.textures / self.cloths / self.targets: plain attributes on the float hand-over; after a compact batch they are
+    # materialised from it on first use (compute_visuals, the data-parallel style context), never on the training path
+    def _lazy(name):
+        def get(self):
+            if getattr(self, "_" + name, None) is None and getattr(self, "_compact", None) is not None:
+                from ..datasets.gpu_texture_batch import expand_batch
+                ref = expand_batch(self.backend.ctx, self._compact, self.opt.cloth_channels)
+                self._textures, self._cloths, self._targets = ref["input_textures"], ref["cloths"], ref["target_textures"]
+            return getattr(self, "_" + name)
+
+        def set(self, v):
+            setattr(self, "_" + name, v)
+        return property(get, set)
+
+    textures, cloths, targets = _lazy("textures"), _lazy("cloths"), _lazy("targets")
+    del _lazy
+
+    def _set_input_compact(self, input):
+        """The compact batch of datasets.gpu_texture_batch.GpuTextureBatch.collate: every slot in one device launch."""
+        B = input["textures_u8"].shape[0]
+        _, _, W, H = input["crop"]
+        m = self.backend.ensure(B, H, W)
+        m.set_input_texture_batch(input)
+        self._compact = input
+        self.textures = self.cloths = self.targets = None
+        self.rois = input["rois_raw"]
+        self.image_paths = tuple(zip(input["cloth_paths"], input["texture_paths"]))
+        self._fakes = None
+
     def set_input(self, input):
         """texture_model.py:113-119."""
+        if "textures_u8" in input:
+            return self._set_input_compact(input)
+        self._compact = None
         self.textures, self.rois, self.cloths = input["input_textures"], input["rois"], input["cloths"]
         B, _, H, W = self.textures.shape
         m = self.backend.ensure(B, H, W)
