@@ -39,7 +39,8 @@ typedef struct swn_ctx swn_ctx;
 typedef struct swn_model swn_model;
 
 int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lambda_gp; 4: swn_route_*, swn_model_step_captured, swn_model_create_shared;
-                                5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit; 8: swn_op_loss, swn_op_bias_grad */
+                                5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit; 8: swn_op_loss, swn_op_bias_grad;
+                                9: swn_op_norm_act, swn_op_elementwise, swn_op_resample */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -449,6 +450,34 @@ int swn_op_norm_act_dropout(swn_ctx* ctx, const float* x, const float* dy, int n
  * backward, returns uy = d<gx,u>/d gy and ax = d<gx,u>/d x.  NCHW fp32, C % 4 == 0. */
 int swn_op_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const float* u, int n, int c, int h, int w, int act,
                          float* uy, float* ax);
+/* The kernels between the convolutions, each launcher of ops.h called alone on channel-slice views (tests).  Convention of the three
+ * entry points below: tensors are NCHW device floats; every operand lives in an NHWC buffer of lead + c + pad channels (lead, pad
+ * multiples of 4, given per operand in `lead_pad` = {lead, pad} pairs), every byte of which holds 0x7f before the logical channels
+ * are loaded, and the launcher gets buffer.slice(lead, c).  The optional *_buf outputs receive the WHOLE buffer afterwards as
+ * (n, lead + c + pad, h, w): its non-logical channels must still hold 0x7f7f7f7f.  Amax slots are 256 floats, zeroed before the call.
+ *
+ * swn_op_norm_act: norm_act_fwd, then (dy and dx given) norm_act_bwd on the same x and stats.  lead_pad[10] = x, y, dy, dx, residual.
+ * seed_on_device != 0: the kernels read `seed` from device memory and use seed * 0x9E3779B1 + salt (NormActArgs::seed_base), else
+ * `seed` itself.  partial_in (optional, device doubles [n][partial_chunks][c][2]): the statistics' partial sums (finalize + apply,
+ * no statistics pass).  want_colsum 0: no column sums; 1: request them where norm_act_bwd_emits_colsum(h * w, c) holds; 2: request
+ * them regardless (the launcher refuses where it cannot emit them).  *colsum_emitted (host int) = whether they were requested and
+ * written: then colsum = (n, c) device doubles and db = c device floats = bias_grad_from_colsums(colsum).  stats = (n, c, 2).
+ * y == NULL: the backward pass alone, with the (mean, rstd) pairs the caller put into `stats`. */
+int swn_op_norm_act(swn_ctx* ctx, const float* x, const float* dy, const float* residual, int n, int c, int h, int w, int norm,
+                    int act, float drop_p, uint64_t seed, int seed_on_device, uint64_t salt, const double* partial_in,
+                    int partial_chunks, const int* lead_pad, int want_colsum, float* y, float* stats, float* y_slot, float* dx,
+                    float* dx_slot, double* colsum, int* colsum_emitted, float* db, float* y_buf, float* dx_buf);
+/* op 0: act_fwd(a) ; 1: act_bwd(dy = a, y = b) ; 2: axpy(src = a, alpha, shift).  lead_pad[6] = a, b, out.  accumulate != 0 (ops 1, 2):
+ * the incoming contents of `out` are loaded first and the kernel adds to them.  slot (optional): the amax slot of what was written. */
+int swn_op_elementwise(swn_ctx* ctx, int op, const float* a, const float* b, int n, int c, int h, int w, int act, int accumulate,
+                       float alpha, float shift, const int* lead_pad, float* out, float* slot, float* out_buf);
+/* (n, c, h, w) is the shape of a.  op 0: upsample_nearest_fwd, out (h * factor, w * factor) ; 1: upsample_nearest_bwd, a = dy, out
+ * (h / factor, w / factor) ; 2: maxpool2_fwd, out (h / 2, w / 2), pattern = pool_pattern ; 3: maxpool2_bwd, a = x, b = dy (h / 2,
+ * w / 2), out = dx (h, w), pattern = pool_pattern ; 4: reflect_fold, a = the (h, w) gradient of the padded tensor, out (h - 2, w - 2) ;
+ * 5: act_pattern of a (no out).  pattern (optional): device bytes, NCHW of the pooled map (ops 2, 3) or of a (op 5).
+ * lead_pad[6] = a, b, out; accumulate (ops 1, 3, 4) and slot (ops 0, 2) as in swn_op_elementwise. */
+int swn_op_resample(swn_ctx* ctx, int op, const float* a, const float* b, int n, int c, int h, int w, int factor, int accumulate,
+                    const int* lead_pad, float* out, float* slot, uint8_t* pattern, float* out_buf);
 /* torch.optim.AdamW single step on flat arrays (optimizers/__init__.py:52-59) */
 int swn_op_adamw(swn_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2,
                  float eps, float wd, int step);

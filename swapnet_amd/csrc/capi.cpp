@@ -59,7 +59,7 @@ static int guard(F f) {
 
 extern "C" {
 
-int swn_abi_version(void) { return 8; }
+int swn_abi_version(void) { return 9; }
 const char* swn_last_error(void) { return g_err.c_str(); }
 int swn_is_device_build(void) { return is_device_build(); }
 
@@ -956,6 +956,156 @@ int swn_op_bias_grad(swn_ctx* ctx, const float* dy, int n, int c, int h, int w, 
     float* out = static_cast<float*>(tmp.alloc((size_t)c * sizeof(float)));
     bias_grad(s, yv.v.slice(0, c), out);
     dev_copy(s, db, out, (size_t)c * sizeof(float));
+    stream_sync(s);
+  });
+}
+// ---- the kernels between the convolutions on channel-slice views (swapnet_hip.h: swn_op_norm_act / _elementwise / _resample) ----
+// one operand: an (N,H,W,lead + c + pad) buffer, every byte the sentinel, the logical channels loaded into slice(lead, c)
+struct OpBuf { TView whole, v; };
+static OpBuf op_buf(Net& net, Stream& s, int n, int h, int w, int c, const int* lp, const float* nchw) {
+  REQUIRE(lp[0] >= 0 && lp[1] >= 0 && lp[0] % 4 == 0 && lp[1] % 4 == 0, "lead_c and pad_c must be non-negative multiples of 4");
+  OpBuf b;
+  b.whole = net.alloc_var(n, h, w, lp[0] + c + lp[1], false).v;
+  dev_memset(s, b.whole.p, kPadSentinelByte, b.whole.pixels() * b.whole.cs * sizeof(float));
+  b.v = b.whole.slice(lp[0], c);
+  if (nchw) nchw_to_nhwc(s, nchw, n, c, h, w, b.v);
+  return b;
+}
+static void op_buf_out(Stream& s, const OpBuf& b, float* nchw, float* whole_nchw) {
+  if (nchw) nhwc_to_nchw(s, b.v, nchw, b.v.C);
+  if (whole_nchw) nhwc_to_nchw(s, b.whole, whole_nchw, b.whole.C);
+}
+static float* op_slot(Ctx& tmp, bool want) {
+  if (!want) return nullptr;
+  float* p = static_cast<float*>(tmp.alloc(AMAX_SLOT * sizeof(float)));
+  dev_memset(tmp.s, p, 0, AMAX_SLOT * sizeof(float));
+  return p;
+}
+int swn_op_norm_act(swn_ctx* ctx, const float* x, const float* dy, const float* residual, int n, int c, int h, int w, int norm,
+                    int act, float drop_p, uint64_t seed, int seed_on_device, uint64_t salt, const double* partial_in,
+                    int partial_chunks, const int* lead_pad, int want_colsum, float* y, float* stats, float* y_slot, float* dx,
+                    float* dx_slot, double* colsum, int* colsum_emitted, float* db, float* y_buf, float* dx_buf) {
+  return guard([&] {
+    REQUIRE(ctx && x && lead_pad && (y || dy), "NULL argument");
+    REQUIRE(y || !norm || stats, "the backward pass alone (y == NULL) takes the statistics from `stats`");
+    REQUIRE(n > 0 && c > 0 && c % 4 == 0 && h > 0 && w > 0, "bad shape (C must be a multiple of 4)");
+    REQUIRE(act >= 0 && act <= 3 && drop_p >= 0.f && drop_p < 1.f, "bad activation / dropout probability must be in [0, 1)");
+    REQUIRE((dy != nullptr) == (dx != nullptr), "dy and dx go together");
+    REQUIRE(want_colsum >= 0 && want_colsum <= 2 && (!want_colsum || dy), "bad want_colsum (column sums belong to the backward pass)");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Stream& s = tmp.s;
+    OpBuf xb = op_buf(net, s, n, h, w, c, lead_pad, x), yb = op_buf(net, s, n, h, w, c, lead_pad + 2, nullptr), rb;
+    if (residual) rb = op_buf(net, s, n, h, w, c, lead_pad + 8, residual);
+    float* st = static_cast<float*>(tmp.alloc((size_t)n * c * 2 * sizeof(float)));
+    uint64_t* seed_dev = nullptr;
+    if (seed_on_device) {
+      seed_dev = static_cast<uint64_t*>(tmp.alloc(sizeof(uint64_t)));
+      dev_upload(s, seed_dev, &seed, sizeof(uint64_t));
+    }
+    NormActArgs a;
+    a.x = xb.v; a.y = yb.v; a.stats = st; a.norm = norm; a.act = act; a.drop_p = drop_p;
+    a.seed = seed_on_device ? 0 : seed; a.seed_base = seed_dev; a.salt = salt;
+    a.residual = residual ? &rb.v : nullptr;
+    a.amax_out = op_slot(tmp, y && y_slot);
+    a.partial_in = partial_in; a.partial_chunks = partial_chunks;
+    if (y) {
+      norm_act_fwd(s, a);
+      op_buf_out(s, yb, y, y_buf);
+      if (stats && norm) dev_copy(s, stats, st, (size_t)n * c * 2 * sizeof(float));
+      if (y_slot) dev_copy(s, y_slot, a.amax_out, AMAX_SLOT * sizeof(float));
+    } else if (norm) {
+      dev_copy(s, st, stats, (size_t)n * c * 2 * sizeof(float));
+    }
+    if (colsum_emitted) *colsum_emitted = 0;
+    if (dy) {
+      OpBuf gb = op_buf(net, s, n, h, w, c, lead_pad + 4, dy), db_ = op_buf(net, s, n, h, w, c, lead_pad + 6, nullptr);
+      const bool ask = want_colsum == 2 || (want_colsum == 1 && norm && norm_act_bwd_emits_colsum(h * w, c));
+      NormActBwdArgs b;
+      b.dy = gb.v; b.x = xb.v; b.stats = st; b.dx = db_.v; b.norm = norm; b.act = act; b.drop_p = drop_p;
+      b.seed = a.seed; b.seed_base = seed_dev; b.salt = salt;
+      b.colsum = ask ? static_cast<double*>(tmp.alloc((size_t)n * c * sizeof(double))) : nullptr;
+      b.amax_out = op_slot(tmp, dx_slot != nullptr);
+      norm_act_bwd(s, b);
+      op_buf_out(s, db_, dx, dx_buf);
+      if (dx_slot) dev_copy(s, dx_slot, b.amax_out, AMAX_SLOT * sizeof(float));
+      if (ask) {
+        if (colsum_emitted) *colsum_emitted = 1;
+        if (colsum) dev_copy(s, colsum, b.colsum, (size_t)n * c * sizeof(double));
+        if (db) {
+          float* o = static_cast<float*>(tmp.alloc((size_t)c * sizeof(float)));
+          bias_grad_from_colsums(s, b.colsum, n, c, o);
+          dev_copy(s, db, o, (size_t)c * sizeof(float));
+        }
+      }
+    }
+    stream_sync(s);
+  });
+}
+int swn_op_elementwise(swn_ctx* ctx, int op, const float* a, const float* b, int n, int c, int h, int w, int act, int accumulate,
+                       float alpha, float shift, const int* lead_pad, float* out, float* slot, float* out_buf) {
+  return guard([&] {
+    REQUIRE(ctx && a && out && lead_pad && (op != 1 || b), "NULL argument");
+    REQUIRE(op >= 0 && op <= 2 && act >= 0 && act <= 3, "bad op / activation");
+    REQUIRE(n > 0 && c > 0 && c % 4 == 0 && h > 0 && w > 0, "bad shape (C must be a multiple of 4)");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Stream& s = tmp.s;
+    OpBuf ab = op_buf(net, s, n, h, w, c, lead_pad, a), bb;
+    if (op == 1) bb = op_buf(net, s, n, h, w, c, lead_pad + 2, b);
+    OpBuf ob = op_buf(net, s, n, h, w, c, lead_pad + 4, (op != 0 && accumulate) ? out : nullptr);
+    float* sl = op_slot(tmp, slot != nullptr);
+    if (op == 0) act_fwd(s, ab.v, ob.v, act, sl);
+    else if (op == 1) act_bwd(s, ab.v, bb.v, ob.v, act, accumulate, sl);
+    else axpy(s, ab.v, ob.v, alpha, accumulate, shift, sl);
+    op_buf_out(s, ob, out, out_buf);
+    if (slot) dev_copy(s, slot, sl, AMAX_SLOT * sizeof(float));
+    stream_sync(s);
+  });
+}
+int swn_op_resample(swn_ctx* ctx, int op, const float* a, const float* b, int n, int c, int h, int w, int factor, int accumulate,
+                    const int* lead_pad, float* out, float* slot, uint8_t* pattern, float* out_buf) {
+  return guard([&] {
+    REQUIRE(ctx && a && lead_pad && (out || op == 5) && (op != 3 || b), "NULL argument");
+    REQUIRE(op >= 0 && op <= 5, "bad op");
+    REQUIRE(n > 0 && c > 0 && c % 4 == 0 && h > 0 && w > 0, "bad shape (C must be a multiple of 4)");
+    if (op >= 2) factor = 2;
+    REQUIRE(factor >= 1 && (op == 0 || op >= 4 || (h % factor == 0 && w % factor == 0)), "bad factor (h and w must be multiples of it)");
+    REQUIRE(op != 4 || (h > 2 && w > 2), "reflect_fold: the padded gradient is at least 3 x 3");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Stream& s = tmp.s;
+    // geometry of the output and of the pooled map
+    const int ho = op == 0 ? h * factor : (op == 1 || op == 2) ? h / factor : op == 4 ? h - 2 : h;
+    const int wo = op == 0 ? w * factor : (op == 1 || op == 2) ? w / factor : op == 4 ? w - 2 : w;
+    OpBuf ab = op_buf(net, s, n, h, w, c, lead_pad, a);
+    float* sl = op_slot(tmp, slot != nullptr);
+    uint8_t* pat = nullptr;
+    const size_t pat_bytes = (size_t)n * c * (op == 5 ? (size_t)h * w : (size_t)(h / 2) * (w / 2));
+    if (pattern) {
+      REQUIRE(op == 2 || op == 3 || op == 5, "this op has no pattern");
+      pat = static_cast<uint8_t*>(tmp.alloc(pat_bytes));
+    }
+    if (op == 5) {
+      REQUIRE(pattern, "act_pattern: pattern is NULL");
+      act_pattern(s, ab.v, pat);
+    } else {
+      OpBuf ob = op_buf(net, s, n, ho, wo, c, lead_pad + 4, accumulate && (op == 1 || op == 3 || op == 4) ? out : nullptr);
+      if (op == 0) upsample_nearest_fwd(s, ab.v, ob.v, factor, sl);
+      else if (op == 1) upsample_nearest_bwd(s, ab.v, ob.v, factor, accumulate);
+      else if (op == 2) {
+        maxpool2_fwd(s, ab.v, ob.v, sl);
+        if (pat) pool_pattern(s, ab.v, ob.v, pat);
+      } else if (op == 3) {
+        OpBuf gb = op_buf(net, s, n, h / 2, w / 2, c, lead_pad + 2, b), yb = op_buf(net, s, n, h / 2, w / 2, c, lead_pad + 2, nullptr);
+        maxpool2_fwd(s, ab.v, yb.v, nullptr);
+        maxpool2_bwd(s, gb.v, ab.v, yb.v, ob.v, accumulate);
+        if (pat) pool_pattern(s, ab.v, yb.v, pat);
+      } else reflect_fold(s, ab.v, ob.v, accumulate);
+      op_buf_out(s, ob, out, out_buf);
+    }
+    if (pat) dev_copy(s, pattern, pat, pat_bytes);
+    if (slot) dev_copy(s, slot, sl, AMAX_SLOT * sizeof(float));
     stream_sync(s);
   });
 }

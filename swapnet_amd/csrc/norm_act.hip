@@ -1,8 +1,10 @@
 // swapnet_amd -- InstanceNorm2d (eps 1e-5, biased variance, no affine) + activation +
 // dropout (+ residual add), forward and backward, on NHWC views.  HBM-bound kernels:
 // every access is a 16-byte channel-contiguous load/store, statistics are accumulated in
-// fp64 (no E[x^2]-E[x]^2 cancellation), partial sums are combined in a fixed order so the
-// result is run-to-run deterministic.
+// fp64 as sums of x - x0 and (x - x0)^2 with x0 = the plane's first pixel (E[x^2] - E[x]^2 on the raw
+// values loses (mean / std)^2 * 2^-53 of the variance: a mean-100 / std-0.01 plane came out 1.6 fp32
+// roundings off in rstd), partial sums are combined in a fixed order so the result is run-to-run
+// deterministic.
 // Reference: modules/layers.py:12-44,126-144 (UNetDown / UNetUp / ResidualBlock),
 // modules/__init__.py:66-69 (InstanceNorm2d(affine=False, track_running_stats=False)).
 #include "hip_util.h"
@@ -38,6 +40,7 @@ struct NAp {
   const uint64_t* seed_base;    // captured step: the step seed lives in device memory; seed = *seed_base * 0x9E3779B1 + salt
   uint64_t salt;
   int pair_xcd;                 // in_fused_group
+  int shift;                    // statistics pass: the partials are sums over x - x0, x0 = pixel 0 of the image (0: raw sums, partial_in)
 };
 __device__ __forceinline__ uint64_t na_seed(const NAp& p) { return p.seed_base ? *p.seed_base * 0x9E3779B1ull + p.salt : p.seed; }
 
@@ -54,6 +57,11 @@ __global__ __launch_bounds__(256) void in_partial_kernel(NAp p) {
   double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
   if (ty < rows) {
     float mean[4] = {0, 0, 0, 0}, rstd[4] = {1, 1, 1, 1};
+    double x0[4] = {0, 0, 0, 0};
+    if (MODE == 0 && p.shift) {
+      const float4 f = *reinterpret_cast<const float4*>(p.x + (size_t)n * p.HW * p.xcs + tx * 4);
+      x0[0] = f.x; x0[1] = f.y; x0[2] = f.z; x0[3] = f.w;
+    }
     if (MODE == 1 && p.norm) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -67,7 +75,7 @@ __global__ __launch_bounds__(256) void in_partial_kernel(NAp p) {
       const float xa[4] = {xv.x, xv.y, xv.z, xv.w};
       if (MODE == 0) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { s[j] += xa[j]; ss[j] += (double)xa[j] * xa[j]; }
+        for (int j = 0; j < 4; ++j) { const double d = (double)xa[j] - x0[j]; s[j] += d; ss[j] += d * d; }
       } else {
         const float4 gv = *reinterpret_cast<const float4*>(p.dy + e * p.dycs + tx * 4);
         const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
@@ -105,10 +113,11 @@ __global__ void in_finalize_kernel(NAp p) {
     a += o[0]; b += o[1];
   }
   if (MODE == 0) {
-    const double mean = a / p.HW;
-    double var = b / p.HW - mean * mean;
+    const double x0 = p.shift ? (double)p.x[(size_t)n * p.HW * p.xcs + c] : 0.0;
+    const double md = a / p.HW;
+    double var = b / p.HW - md * md;
     if (var < 0) var = 0;
-    p.stats[(size_t)i * 2] = (float)mean;
+    p.stats[(size_t)i * 2] = (float)(x0 + md);
     p.stats[(size_t)i * 2 + 1] = (float)(1.0 / sqrt(var + (double)IN_EPS));
   } else {
     p.sums[(size_t)i * 2] = a / p.HW;
@@ -308,6 +317,7 @@ __global__ __launch_bounds__(256) void in_fused_fwd_kernel(NAp p) {
   const int n = blockIdx.y, c = in_fused_group<CG>(p.pair_xcd) * CG + tx * 4;
   float4 v[NP];
   double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const float4 x0v = *reinterpret_cast<const float4*>(p.x + (size_t)n * p.HW * p.xcs + c);      // pixel 0: the shift of the sums
   // all loads first, unconditionally (rows past the map re-read its last pixel and are masked below): inside `if (pix < HW)`
   // every load sits in its own basic block and the NP round trips to HBM serialise
 #pragma unroll
@@ -317,19 +327,21 @@ __global__ __launch_bounds__(256) void in_fused_fwd_kernel(NAp p) {
   }
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    const float k = ty + i * ROWS < p.HW ? 1.f : 0.f;
-    const float a0 = v[i].x * k, a1 = v[i].y * k, a2 = v[i].z * k, a3 = v[i].w * k;
+    const double k = ty + i * ROWS < p.HW ? 1.0 : 0.0;
+    const double a0 = ((double)v[i].x - (double)x0v.x) * k, a1 = ((double)v[i].y - (double)x0v.y) * k;
+    const double a2 = ((double)v[i].z - (double)x0v.z) * k, a3 = ((double)v[i].w - (double)x0v.w) * k;
     s[0] += a0; s[1] += a1; s[2] += a2; s[3] += a3;
-    s[4] += (double)a0 * a0; s[5] += (double)a1 * a1; s[6] += (double)a2 * a2; s[7] += (double)a3 * a3;
+    s[4] += a0 * a0; s[5] += a1 * a1; s[6] += a2 * a2; s[7] += a3 * a3;
   }
   block_tree_sum<ROWS, 8>(red, s, tx, ty, C4);
   float mean[4], rstd[4];
+  const float x0a[4] = {x0v.x, x0v.y, x0v.z, x0v.w};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const double m = s[j] / p.HW;
     double var = s[4 + j] / p.HW - m * m;
     if (var < 0) var = 0;
-    mean[j] = (float)m; rstd[j] = (float)(1.0 / sqrt(var + (double)IN_EPS));
+    mean[j] = (float)((double)x0a[j] + m); rstd[j] = (float)(1.0 / sqrt(var + (double)IN_EPS));
   }
   if (ty == 0) {
     float* st = p.stats + ((size_t)n * p.C + c) * 2;
@@ -596,6 +608,7 @@ void norm_act_fwd(Stream& s, const NormActArgs& a) {
   p.norm = a.norm; p.act = a.act; p.drop_p = a.drop_p; p.seed = a.seed;
   p.amax_out = a.amax_out; p.seed_base = a.seed_base; p.salt = a.salt;
   if (a.norm && !a.stats) throw Error(1, "norm_act_fwd: stats buffer required");
+  p.shift = a.partial_in ? 0 : 1;
   p.pair_xcd = (p.C % 256 == 0 && env_on(getenv("SWN_IN_PAIR_XCD"))) ? 1 : 0;
   if (a.norm && !a.partial_in && p.HW <= 1024 && p.C % 32 == 0 && fused_in_on()) {
     const dim3 grid(p.C / 32, p.N);
@@ -629,6 +642,7 @@ void norm_act_fwd(Stream& s, const NormActArgs& a) {
 
 void norm_act_bwd(Stream& s, const NormActBwdArgs& a) {
   check_view4(a.x, "norm_act_bwd x"); check_view4(a.dy, "norm_act_bwd dy"); check_view4(a.dx, "norm_act_bwd dx");
+  if (a.x.C > 1024) throw Error(1, "norm_act: C > 1024 unsupported");      // (C / 4 > 256 threads: in_partial_kernel would have no rows)
   NAp p{};
   p.x = a.x.p; p.xcs = a.x.cs; p.dy = a.dy.p; p.dycs = a.dy.cs; p.y = a.dx.p; p.ycs = a.dx.cs;
   p.stats = const_cast<float*>(a.stats); p.N = a.x.N; p.HW = a.x.H * a.x.W; p.C = a.x.C;

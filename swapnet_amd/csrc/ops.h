@@ -274,7 +274,8 @@ void norm_act_fwd(Stream& s, const NormActArgs& a);
 
 struct NormActBwdArgs {
   TView dy;                   // grad wrt y (view, same geometry as y)
-  TView x;                    // raw conv output saved by forward (norm) or y itself (!norm)
+  TView x;                    // the forward's INPUT x (raw conv output), with and without norm: act' is taken from (x - mean) * rstd,
+                              // or from x itself when !norm (tanh: 1 - tanh(x)^2) -- never the output y (tests/test_norm_act_ops.py)
   const float* stats = nullptr;
   TView dx;                   // grad wrt raw conv output (dense), overwritten
   int norm = 1;

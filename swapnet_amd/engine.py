@@ -544,7 +544,7 @@ def op_gan_loss(ctx, pred, gan_mode, label, target_is_real, grad_scale=1.0, want
 
 
 LOSS_CE, LOSS_L1, LOSS_NORMED_MSE, LOSS_GRAM = 0, 1, 2, 3
-PAD_SENTINEL = 0x7F7F7F7F           # what swn_op_loss / swn_op_bias_grad put into every pad channel before the call
+PAD_SENTINEL = 0x7F7F7F7F           # what swn_op_loss / swn_op_bias_grad / the view-level swn_op_* put into every pad channel before the call
 
 
 def op_loss(ctx, kind, a, b, pad_c=0, scale=1.0, accumulate=False, n0=0, nloc=-1, grad=None, want_grad=True, want_pad=True):
@@ -599,6 +599,99 @@ def op_texture_batch(ctx, textures_u8, labels_u8, rois_raw, sample_params, mean,
                  _C.ptr(rois), rois.shape[1], _C.ptr(sample), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(x_min), int(y_min),
                  int(height), int(width), int(cloth_channels), _C.ptr(inp), _C.ptr(tgt), _C.ptr(cloths), _C.ptr(out))
     return inp, tgt, cloths, out
+
+
+AMAX_SLOT = 256                     # floats of one amax slot (ops.h)
+EW_ACT_FWD, EW_ACT_BWD, EW_AXPY = 0, 1, 2
+RS_UPSAMPLE_FWD, RS_UPSAMPLE_BWD, RS_MAXPOOL_FWD, RS_MAXPOOL_BWD, RS_REFLECT_FOLD, RS_ACT_PATTERN = 0, 1, 2, 3, 4, 5
+
+
+def _dev(ctx, t, dtype=torch.float32):
+    return None if t is None else t.detach().to(device=ctx.device, dtype=dtype).contiguous()
+
+
+def _lead_pad(views, names):
+    """{name: (lead_c, pad_c)} -> the flat int array of the swn_op_* view entry points, and the pairs."""
+    views = views or {}
+    unknown = set(views) - set(names)
+    if unknown:
+        raise ValueError("unknown operand(s) %s (have %s)" % (sorted(unknown), list(names)))
+    pairs = [tuple(int(v) for v in views.get(k, (0, 0))) for k in names]
+    return (C.c_int * (2 * len(names)))(*[v for p in pairs for v in p]), dict(zip(names, pairs))
+
+
+def op_norm_act(ctx, x, dy=None, residual=None, norm=True, act=0, drop_p=0.0, seed=0, seed_on_device=False, salt=0,
+                partial_in=None, views=None, want_colsum=1, stats_in=None):
+    """norm_act_fwd (+ norm_act_bwd when dy is given) alone through swn_op_norm_act, every operand a channel-slice view of a
+    sentinel-filled buffer: views = {"x" | "y" | "dy" | "dx" | "residual": (lead_c, pad_c)}.  partial_in: (N, chunks, C, 2) float64.
+    Returns a dict: y, stats (N,C,2), y_slot (256), y_buf (the whole y buffer, N x (lead + C + pad) x H x W) and, with dy: dx, dx_slot,
+    dx_buf, colsum_emitted, colsum (N,C float64) and db (C) when emitted.  stats_in (N,C,2): the backward pass ALONE on these statistics."""
+    xd, dyd, rd = _dev(ctx, x), _dev(ctx, dy), _dev(ctx, residual)
+    n, c, h, w = xd.shape
+    lp, pairs = _lead_pad(views, ("x", "y", "dy", "dx", "residual"))
+    f32 = dict(dtype=torch.float32, device=ctx.device)
+    pin = _dev(ctx, partial_in, torch.float64)
+    chunks = 0
+    if pin is not None:
+        if pin.dim() != 4 or pin.shape[0] != n or pin.shape[2] != c or pin.shape[3] != 2:
+            raise ValueError("partial_in must be (N, chunks, C, 2)")
+        chunks = pin.shape[1]
+    r = {"y": torch.empty((n, c, h, w), **f32), "stats": torch.empty((n, c, 2), **f32) if norm else None,
+         "y_slot": torch.empty(AMAX_SLOT, **f32), "y_buf": torch.empty((n, sum(pairs["y"]) + c, h, w), **f32),
+         "dx": None, "dx_slot": None, "dx_buf": None, "colsum": None, "db": None, "colsum_emitted": False}
+    if dyd is not None:
+        r.update(dx=torch.empty((n, c, h, w), **f32), dx_slot=torch.empty(AMAX_SLOT, **f32),
+                 dx_buf=torch.empty((n, sum(pairs["dx"]) + c, h, w), **f32),
+                 colsum=torch.empty((n, c), dtype=torch.float64, device=ctx.device), db=torch.empty(c, **f32))
+    if stats_in is not None:
+        r.update(y=None, y_slot=None, y_buf=None, stats=_dev(ctx, stats_in))
+    emitted = C.c_int(0)
+    ctx.lib.call("swn_op_norm_act", ctx.handle, _C.ptr(xd), _C.ptr(dyd), _C.ptr(rd), n, c, h, w, int(bool(norm)), int(act),
+                 C.c_float(drop_p), C.c_uint64(seed), int(bool(seed_on_device)), C.c_uint64(salt), _C.ptr(pin), int(chunks), lp,
+                 int(want_colsum) if dyd is not None else 0, _C.ptr(r["y"]), _C.ptr(r["stats"]), _C.ptr(r["y_slot"]), _C.ptr(r["dx"]),
+                 _C.ptr(r["dx_slot"]), _C.ptr(r["colsum"]), C.byref(emitted), _C.ptr(r["db"]), _C.ptr(r["y_buf"]), _C.ptr(r["dx_buf"]))
+    r["colsum_emitted"] = bool(emitted.value)
+    if not r["colsum_emitted"]:
+        r["colsum"] = r["db"] = None
+    return r
+
+
+def op_elementwise(ctx, op, a, b=None, act=0, accumulate=False, alpha=1.0, shift=0.0, old=None, views=None):
+    """act_fwd / act_bwd (a = dy, b = y) / axpy (a = src) alone through swn_op_elementwise on views = {"a" | "b" | "out": (lead_c,
+    pad_c)}; `old`: the incoming contents of the destination (accumulate).  Returns (out, slot[256], the whole destination buffer)."""
+    ad, bd = _dev(ctx, a), _dev(ctx, b)
+    n, c, h, w = ad.shape
+    lp, pairs = _lead_pad(views, ("a", "b", "out"))
+    out = _dev(ctx, old).clone() if accumulate else torch.empty_like(ad)
+    slot = torch.empty(AMAX_SLOT, dtype=torch.float32, device=ctx.device)
+    buf = torch.empty((n, sum(pairs["out"]) + c, h, w), dtype=torch.float32, device=ctx.device)
+    ctx.lib.call("swn_op_elementwise", ctx.handle, int(op), _C.ptr(ad), _C.ptr(bd), n, c, h, w, int(act), int(bool(accumulate)),
+                 C.c_float(alpha), C.c_float(shift), lp, _C.ptr(out), _C.ptr(slot), _C.ptr(buf))
+    return out, slot, buf
+
+
+def op_resample(ctx, op, a, b=None, factor=2, accumulate=False, old=None, views=None, want_pattern=True):
+    """One resampling launcher alone through swn_op_resample (RS_*; include/swapnet_hip.h gives the shapes) on views = {"a" | "b" |
+    "out": (lead_c, pad_c)}.  Returns (out, slot[256] or None, pattern (uint8) or None, the whole destination buffer)."""
+    ad, bd = _dev(ctx, a), _dev(ctx, b)
+    n, c, h, w = ad.shape
+    lp, pairs = _lead_pad(views, ("a", "b", "out"))
+    f = int(factor)
+    ho, wo = {RS_UPSAMPLE_FWD: (h * f, w * f), RS_UPSAMPLE_BWD: (h // max(f, 1), w // max(f, 1)), RS_MAXPOOL_FWD: (h // 2, w // 2),
+              RS_MAXPOOL_BWD: (h, w), RS_REFLECT_FOLD: (h - 2, w - 2), RS_ACT_PATTERN: (h, w)}[op]
+    f32 = dict(dtype=torch.float32, device=ctx.device)
+    out = slot = pat = buf = None
+    if op != RS_ACT_PATTERN:
+        out = _dev(ctx, old).clone() if accumulate else torch.empty((n, c, max(ho, 0), max(wo, 0)), **f32)
+        assert tuple(out.shape) == (n, c, max(ho, 0), max(wo, 0))
+        buf = torch.empty((n, sum(pairs["out"]) + c, max(ho, 0), max(wo, 0)), **f32)
+    if op in (RS_UPSAMPLE_FWD, RS_MAXPOOL_FWD):
+        slot = torch.empty(AMAX_SLOT, **f32)
+    if op == RS_ACT_PATTERN or (want_pattern and op in (RS_MAXPOOL_FWD, RS_MAXPOOL_BWD)):
+        pat = torch.empty((n, c, h, w) if op == RS_ACT_PATTERN else (n, c, h // 2, w // 2), dtype=torch.uint8, device=ctx.device)
+    ctx.lib.call("swn_op_resample", ctx.handle, int(op), _C.ptr(ad), _C.ptr(bd), n, c, h, w, f, int(bool(accumulate)), lp,
+                 _C.ptr(out), _C.ptr(slot), _C.ptr(pat), _C.ptr(buf))
+    return out, slot, pat, buf
 
 
 def op_norm_act_bwd2(ctx, x, gy, u, act=1):

@@ -816,6 +816,7 @@ void bias_grad(Stream&, const TView& dy, float* db) {
 
 void reflect_fold(Stream&, const TView& sp, const TView& d, int accumulate) {
   const int H = d.H, W = d.W;
+  if (sp.H != H + 2 || sp.W != W + 2 || sp.C != d.C || H < 4 || W < 4) throw Error(1, "reflect_fold: shape mismatch");
   if (!accumulate)
     for (size_t e = 0; e < d.pixels(); ++e) std::memset(d.p + e * d.cs, 0, d.C * sizeof(float));
   for (int n = 0; n < d.N; ++n)
@@ -869,14 +870,25 @@ void norm_act_fwd(Stream&, const NormActArgs& a0) { SIM_TIMED;
   NormActArgs a = a0;
   if (a.seed_base) a.seed = *a.seed_base * 0x9E3779B1ull + a.salt;       // captured-step form of the seed (ops.h)
   const int N = a.x.N, HW = a.x.H * a.x.W, C = a.x.C;
+  if (C > 1024) throw Error(1, "norm_act: C > 1024 unsupported");
   for (int n = 0; n < N; ++n)
     for (int c = 0; c < C; ++c) {
       float mean = 0.f, rstd = 1.f;
       if (a.norm) {
         double s = 0, ss = 0;
-        for (int p = 0; p < HW; ++p) { const double v = a.x.p[((size_t)n * HW + p) * a.x.cs + c]; s += v; ss += v * v; }
-        const double m = s / HW; double var = ss / HW - m * m; if (var < 0) var = 0;
-        mean = (float)m; rstd = (float)(1.0 / std::sqrt(var + 1e-5));
+        if (a.partial_in) {          // the caller's partial sums, added in chunk order as in_finalize_kernel does
+          if (a.partial_chunks <= 0 || HW % a.partial_chunks) throw Error(1, "norm_act_fwd: bad partial_chunks");
+          for (int ch = 0; ch < a.partial_chunks; ++ch) {
+            const double* o = a.partial_in + (((size_t)n * a.partial_chunks + ch) * C + c) * 2;
+            s += o[0]; ss += o[1];
+          }
+        }
+        // sums of x - x0, x0 = the plane's first pixel: E[x^2] - E[x]^2 on the raw values loses (mean / std)^2 * 2^-53 of the variance
+        const double x0 = a.partial_in ? 0.0 : (double)a.x.p[(size_t)n * HW * a.x.cs + c];
+        if (!a.partial_in)
+          for (int p = 0; p < HW; ++p) { const double v = (double)a.x.p[((size_t)n * HW + p) * a.x.cs + c] - x0; s += v; ss += v * v; }
+        const double md = s / HW, m = x0 + md; double var = ss / HW - md * md; if (var < 0) var = 0;
+        mean = (float)m; rstd = (float)(1.0 / std::sqrt(var + (double)1e-5f));      // eps is the fp32 constant, as norm_act.hip IN_EPS
         a.stats[((size_t)n * C + c) * 2] = mean; a.stats[((size_t)n * C + c) * 2 + 1] = rstd;
       }
       for (int p = 0; p < HW; ++p) {
@@ -894,6 +906,8 @@ void norm_act_bwd(Stream&, const NormActBwdArgs& a0) { SIM_TIMED;
   NormActBwdArgs a = a0;
   if (a.seed_base) a.seed = *a.seed_base * 0x9E3779B1ull + a.salt;
   const int N = a.x.N, HW = a.x.H * a.x.W, C = a.x.C;
+  if (C > 1024) throw Error(1, "norm_act: C > 1024 unsupported");
+  if (a.colsum) throw Error(1, "norm_act_bwd: colsum requested on the chunked path");       // (norm_act_bwd_emits_colsum is false here)
   for (int n = 0; n < N; ++n)
     for (int c = 0; c < C; ++c) {
       float mean = 0.f, rstd = 1.f;
@@ -963,7 +977,7 @@ void maxpool2_fwd(Stream&, const TView& x, const TView& y, float* amax_out) {
   for (int n = 0; n < y.N; ++n) for (int oy = 0; oy < y.H; ++oy) for (int ox = 0; ox < y.W; ++ox)
     for (int c = 0; c < y.C; ++c) {
       float m = at(x, n, oy * 2, ox * 2)[c];
-      for (int t = 1; t < 4; ++t) { const float v = at(x, n, oy * 2 + (t >> 1), ox * 2 + (t & 1))[c]; if (v > m) m = v; }
+      for (int t = 1; t < 4; ++t) { const float v = at(x, n, oy * 2 + (t >> 1), ox * 2 + (t & 1))[c]; if (v > m || v != v) m = v; }      // (NaN wins, as gather.hip)
       at(y, n, oy, ox)[c] = m;
     }
   sim_fold_view(amax_out, y);
@@ -972,7 +986,7 @@ void maxpool2_bwd(Stream&, const TView& dy, const TView& x, const TView& y, cons
   for (int n = 0; n < y.N; ++n) for (int oy = 0; oy < y.H; ++oy) for (int ox = 0; ox < y.W; ++ox)
     for (int c = 0; c < y.C; ++c) {
       float m = at(x, n, oy * 2, ox * 2)[c]; int am = 0;
-      for (int t = 1; t < 4; ++t) { const float v = at(x, n, oy * 2 + (t >> 1), ox * 2 + (t & 1))[c]; if (v > m) { m = v; am = t; } }
+      for (int t = 1; t < 4; ++t) { const float v = at(x, n, oy * 2 + (t >> 1), ox * 2 + (t & 1))[c]; if (v > m || v != v) { m = v; am = t; } }
       for (int t = 0; t < 4; ++t) { float* d = at(dx, n, oy * 2 + (t >> 1), ox * 2 + (t & 1)) + c; const float v = t == am ? at(dy, n, oy, ox)[c] : 0.f; *d = accumulate ? *d + v : v; }
     }
 }
