@@ -200,9 +200,22 @@ int swn_model_set_input_labels(swn_model* m, int slot, const int32_t* dev_labels
 int swn_model_set_input_texture_batch(swn_model* m, const uint8_t* img, int b, int hs, int ws, const uint8_t* labels, int hl, int wl,
                                       const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3,
                                       int x_min, int y_min);
+/* Warp models: everything swn_model_set_input writes for slots 0 (bodys), 1 (input_cloths) and, when training, 2 (target_cloths) from
+ * the COMPACT batch, one device launch (swn_op_warp_batch below has the arithmetic): body (B,hb,wb,3) uint8 = the decoded RGB images,
+ * NOT resized; in_labels / tgt_labels (B,hl,wl) uint8 = the cloth label maps as stored (tgt_labels may be the same pointer as
+ * in_labels: --dataset_mode image; NULL for an inference model, where nothing of a target is written); maps = doubles
+ * [b * cloth_channels][nmaps][9], the table of swn_op_affine_gather (NULL or nmaps 0: no augmentation) -- all device pointers;
+ * mean3 / std3 = the body statistics, HOST floats.  The crop window is the model's H x W at (x_min, y_min) of the load_size x load_size
+ * resized sample.  Bit-identical to swn_model_set_input on the tensors WarpDataset.__getitem__ builds (datasets/warp_dataset.py:
+ * 139-183) with the per-channel augmentation of swn_op_affine_gather, the operand amax slots included.  RGB bodies only. */
+int swn_model_set_input_warp_batch(swn_model* m, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels,
+                                   const uint8_t* tgt_labels, int hl, int wl, const double* maps, int nmaps, const float* mean3,
+                                   const float* std3, int load_size, int x_min, int y_min);
 /* slot 0: self.fakes (B,19,H,W) warp / (B,3,H,W) texture */
 int swn_model_get_output(swn_model* m, int slot, float* dev_nchw);
-/* named intermediate activation (debug / per-level parity tests), copied out as NCHW */
+/* named intermediate activation (debug / per-level parity tests), copied out as NCHW.  Warp models, net 0, also name the buffers
+ * filled from outside, pad channels included -- "body", "cloth", "Dx" (the conditional-D input [cloth | body], 2B images when
+ * training) -- and their operand amax slots "slot_body", "slot_cloth", "slot_dx" as (1,256,1,1) */
 int swn_model_get_tap(swn_model* m, int net, const char* name, float* dev_nchw, int shape[4]);
 
 /* gradient w.r.t. a named activation as left by the last backward pass through `net` (diagnostics) */
@@ -422,6 +435,27 @@ int swn_op_texture_batch(swn_ctx* ctx, const uint8_t* img, int b, int hs, int ws
                          const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3, int x_min,
                          int y_min, int h, int w, int cloth_channels, float* in_nchw, float* tgt_nchw, float* cloths_nchw,
                          float* rois_out);
+/* WarpDataset.__getitem__ (datasets/warp_dataset.py:139-183) for a whole batch as ONE device launch, from the compact form
+ * (arguments as swn_model_set_input_warp_batch; h x w = the crop window at (x_min, y_min) of the load_size x load_size resized sample).
+ * With (y, x) a pixel of the window, sy = y_min + y, sx = x_min + x, Ls = load_size and
+ * near(d, in) = min(int(floorf(d * (float(in) / Ls))), in - 1)           (F.interpolate(size = Ls), torch's nearest rule):
+ *   target_cloths_nchw (B,cloth_channels,h,w) = one-hot (label 0 and labels >= cloth_channels: all zero) of
+ *                         tgt_labels[near(sy, hl), near(sx, wl)]                    to_onehot_tensor, F.interpolate, crop
+ *   input_cloths_nchw (B,cloth_channels,h,w): channel c is 1 where channel c's chain of maps, walked backwards from
+ *                         (near(sy, hl), near(sx, wl)) exactly as swn_op_affine_gather walks it on the hl x wl map (16.16 fixed
+ *                         point for kind 1, the double-precision perspective for kind 2), stays inside the map and ends on a pixel
+ *                         with in_labels == c, c != 0; else 0      per_channel_transform of the one-hot map, F.interpolate, crop
+ *   bodys_nchw (B,3,h,w) = bilinear sample (align_corners False) of the texels t = (float(byte) / 255 - mean) / std of the hb x wb
+ *                         image, in fp32, one correctly rounded operation per step, no fused multiply-add:
+ *                           src = max(scale * (d + 0.5f) - 0.5f, 0), scale = float(in) / Ls, for d = sy (in = hb) and d = sx (in = wb)
+ *                           i0 = min(int(src), in - 1), i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1
+ *                           v = h0 * (w0 * t[y0,x0] + w1 * t[y0,x1]) + h1 * (w0 * t[y1,x0] + w1 * t[y1,x1])
+ *                                                       ToTensor, Normalize, F.interpolate(size = Ls, mode = "bilinear"), crop
+ * The float one-hot map of the host chain is never built.  target_cloths_nchw may be NULL (then tgt_labels may be too).  As with
+ * swn_op_affine_gather, RandomPerspective is resampled NEAREST (the reference: BICUBIC); everything else is bit-identical. */
+int swn_op_warp_batch(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int hl,
+                      int wl, const double* maps, int nmaps, const float* mean3, const float* std3, int load_size, int x_min, int y_min,
+                      int h, int w, int cloth_channels, float* bodys_nchw, float* input_cloths_nchw, float* target_cloths_nchw);
 /* GANLoss(gan_mode)(prediction, target_is_real) (modules/loss.py:110-130) with the target scalar already drawn
  * (`label`; the smooth-label draw stays host-side like in the reference, loss.py:65-108): mean BCE-with-logits /
  * MSE / +-mean over ALL elements of pred (N,C,H,W).  loss_out = device float; dpred (optional, same shape) receives

@@ -375,6 +375,14 @@ int swn_model_set_input_texture_batch(swn_model* m, const uint8_t* img, int b, i
     m->m->set_input_texture_batch(img, b, hs, ws, labels, hl, wl, rois_raw, r, sample, mean3, std3, x_min, y_min);
   });
 }
+int swn_model_set_input_warp_batch(swn_model* m, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels,
+                                   const uint8_t* tgt_labels, int hl, int wl, const double* maps, int nmaps, const float* mean3,
+                                   const float* std3, int load_size, int x_min, int y_min) {
+  return guard([&] {
+    REQUIRE(m && body && in_labels && mean3 && std3, "NULL argument");
+    m->m->set_input_warp_batch(body, b, hb, wb, in_labels, tgt_labels, hl, wl, maps, nmaps, mean3, std3, load_size, x_min, y_min);
+  });
+}
 int swn_model_get_output(swn_model* m, int slot, float* dst) {
   return guard([&] { REQUIRE(m && dst, "NULL argument"); m->m->get_output(slot, dst); });
 }
@@ -883,6 +891,32 @@ int swn_op_texture_batch(swn_ctx* ctx, const uint8_t* img, int b, int hs, int ws
     nhwc_to_nchw(tmp.s, a.in_tex, in_nchw, 3);
     nhwc_to_nchw(tmp.s, a.tgt_tex, tgt_nchw, 3);
     nhwc_to_nchw(tmp.s, a.cloth[0], cloths_nchw, cloth_channels);
+    stream_sync(tmp.s);
+  });
+}
+int swn_op_warp_batch(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int hl,
+                      int wl, const double* maps, int nmaps, const float* mean3, const float* std3, int load_size, int x_min, int y_min,
+                      int h, int w, int cloth_channels, float* bodys_nchw, float* input_cloths_nchw, float* target_cloths_nchw) {
+  return guard([&] {
+    REQUIRE(ctx && body && in_labels && mean3 && std3 && bodys_nchw && input_cloths_nchw, "NULL argument");
+    REQUIRE(!target_cloths_nchw || tgt_labels, "warp_batch: target cloths asked for without target label maps");
+    REQUIRE(b > 0 && h > 0 && w > 0, "warp_batch: empty sizes");
+    REQUIRE(cloth_channels >= 2 && cloth_channels <= 64, "warp_batch: cloth channels in [2,64]");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    // one buffer [body texel | input cloth | target cloth], so that every destination is a channel slice like the model's
+    const int cp = round_up(cloth_channels, 4);
+    Var t = net.alloc_var(b, h, w, 4 + 2 * cp, false);
+    WarpBatchArgs a;
+    a.body = body; a.Hb = hb; a.Wb = wb; a.in_labels = in_labels; a.Hl = hl; a.Wl = wl; a.maps = maps; a.nmaps = nmaps;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.std[c] = std3[c]; }
+    a.Ls = load_size; a.x_min = x_min; a.y_min = y_min; a.C = cloth_channels;
+    a.body_out[0] = t.v.slice(0, 4); a.nbody = 1; a.in_cloth = t.v.slice(4, cp);
+    if (target_cloths_nchw) { a.tgt_labels = tgt_labels; a.tgt_cloth = t.v.slice(4 + cp, cp); }
+    warp_batch(tmp.s, a);
+    nhwc_to_nchw(tmp.s, a.body_out[0], bodys_nchw, 3);
+    nhwc_to_nchw(tmp.s, a.in_cloth, input_cloths_nchw, cloth_channels);
+    if (target_cloths_nchw) nhwc_to_nchw(tmp.s, a.tgt_cloth, target_cloths_nchw, cloth_channels);
     stream_sync(tmp.s);
   });
 }

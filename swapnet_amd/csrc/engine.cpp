@@ -1584,6 +1584,10 @@ void Model::set_input_texture_batch(const uint8_t*, int, int, int, const uint8_t
                                     const float*, int, int) {
   throw Error(1, "set_input_texture_batch: only the texture model takes a texture batch");
 }
+void Model::set_input_warp_batch(const uint8_t*, int, int, int, const uint8_t*, const uint8_t*, int, int, const double*, int, const float*,
+                                 const float*, int, int, int) {
+  throw Error(1, "set_input_warp_batch: only the warp model takes a warp batch");
+}
 void Model::perceptual(const float*, const float*, int, float*, float, float, float*) {
   throw Error(1, "perceptual: only the texture model carries the VGG16 network (not implemented for this model)");
 }
@@ -1782,6 +1786,83 @@ __attribute__((weak)) void texture_batch(Stream&, const TextureBatchArgs& a) {
       }
       for (int j = 0; j < 4; ++j) out[j] = v[j];
     }
+  }
+}
+
+// Host form of the warp batch hand-over (ops.h warp_batch), weak like texture_batch above: the same expressions in the same order as
+// warp_batch.hip.
+__attribute__((weak)) void warp_batch(Stream&, const WarpBatchArgs& a) {
+  warp_batch_check(a);
+  const int B = a.in_cloth.N, H = a.in_cloth.H, W = a.in_cloth.W, Cp = round_up(a.C, 4), nmaps = a.maps ? a.nmaps : 0;
+  const float lscale_y = (float)a.Hl / (float)a.Ls, lscale_x = (float)a.Wl / (float)a.Ls;
+  const float bscale_y = (float)a.Hb / (float)a.Ls, bscale_x = (float)a.Wb / (float)a.Ls;
+  // (volatile: one rounded fp32 operation per step, whatever the compiler's contraction rules)
+  auto mul = [](float x, float y) { volatile float r = x * y; return (float)r; };
+  auto add = [](float x, float y) { volatile float r = x + y; return (float)r; };
+  auto sub = [](float x, float y) { volatile float r = x - y; return (float)r; };
+  auto texel = [&](const uint8_t* px, int c) { volatile float t = (float)px[c] / 255.f; volatile float d = t - a.mean[c]; return d / a.std[c]; };
+  auto bilinear_src = [&](int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
+    const float src = std::fmax(sub(mul(scale, (float)dst + 0.5f), 0.5f), 0.f);
+    i0 = std::min((int)src, in - 1);
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l1 = sub(src, (float)i0);
+    l0 = sub(1.f, l1);
+  };
+  auto walk = [&](int bc, int x0, int y0) {                   // affine_gather's walk: the source pixel's index, or -1 outside
+    long long x = x0, y = y0;
+    for (int k = nmaps - 1; k >= 0; --k) {
+      const double* m = a.maps + ((size_t)bc * nmaps + k) * 9;
+      const int kind = (int)m[0];
+      long long xin = x, yin = y;
+      if (kind == 1) {
+        xin = ((long long)m[3] + (long long)m[2] * y + (long long)m[1] * x) >> 16;
+        yin = ((long long)m[6] + (long long)m[5] * y + (long long)m[4] * x) >> 16;
+      } else if (kind == 2) {
+        const double xc = (double)x + 0.5, yc = (double)y + 0.5;
+        const double den = m[7] * xc + m[8] * yc + 1.0;
+        const double fx = (m[1] * xc + m[2] * yc + m[3]) / den, fy = (m[4] * xc + m[5] * yc + m[6]) / den;
+        xin = fx < 0.0 ? -1 : (long long)(int)fx;
+        yin = fy < 0.0 ? -1 : (long long)(int)fy;
+      }
+      if (!(xin >= 0 && xin < a.Wl && yin >= 0 && yin < a.Hl)) return -1;
+      x = xin; y = yin;
+    }
+    return (int)y * a.Wl + (int)x;
+  };
+  for (int b = 0; b < B; ++b) {
+    const uint8_t* im = a.body + (size_t)b * a.Hb * a.Wb * 3;
+    const size_t lb = (size_t)b * a.Hl * a.Wl;
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const size_t pix = ((size_t)b * H + y) * W + x;
+        const int sy = a.y_min + y, sx = a.x_min + x;
+        int y0, y1, x0, x1; float h0, h1, w0, w1;
+        bilinear_src(sy, bscale_y, a.Hb, y0, y1, h0, h1);
+        bilinear_src(sx, bscale_x, a.Wb, x0, x1, w0, w1);
+        const uint8_t* pa = im + ((size_t)y0 * a.Wb + x0) * 3; const uint8_t* pb = im + ((size_t)y0 * a.Wb + x1) * 3;
+        const uint8_t* pc = im + ((size_t)y1 * a.Wb + x0) * 3; const uint8_t* pd = im + ((size_t)y1 * a.Wb + x1) * 3;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < 3; ++c) {
+          const float top = add(mul(w0, texel(pa, c)), mul(w1, texel(pb, c)));
+          const float bot = add(mul(w0, texel(pc, c)), mul(w1, texel(pd, c)));
+          v[c] = add(mul(h0, top), mul(h1, bot));
+        }
+        for (int k = 0; k < a.nbody; ++k)
+          for (int c = 0; c < 4; ++c) a.body_out[k].p[pix * a.body_out[k].cs + c] = v[c];
+        const int ly = std::min((int)floorf(mul((float)sy, lscale_y)), a.Hl - 1), lx = std::min((int)floorf(mul((float)sx, lscale_x)), a.Wl - 1);
+        if (a.tgt_cloth.p) {
+          const int l = a.tgt_labels[lb + (size_t)ly * a.Wl + lx];
+          float* dst = a.tgt_cloth.p + pix * a.tgt_cloth.cs;
+          for (int c = 0; c < Cp; ++c) dst[c] = (c == l && l != 0 && l < a.C) ? 1.f : 0.f;
+        }
+        float* dst = a.in_cloth.p + pix * a.in_cloth.cs;
+        for (int c = 0; c < Cp; ++c) {
+          dst[c] = 0.f;
+          if (c == 0 || c >= a.C) continue;
+          const int src = walk(b * a.C + c, lx, ly);
+          if (src >= 0 && a.in_labels[lb + src] == c) dst[c] = 1.f;
+        }
+      }
   }
 }
 

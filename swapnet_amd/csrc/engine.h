@@ -410,6 +410,11 @@ class Model {
   virtual void set_input_texture_batch(const uint8_t* img, int N, int Hs, int Ws, const uint8_t* labels, int Hl, int Wl,
                                        const float* rois_raw, int R, const float* sample, const float mean[3], const float std_[3],
                                        int x_min, int y_min);
+  // warp models: every buffer set_input fills for slots 0-2 from the compact batch in one launch (ops.h warp_batch); the crop window is
+  // the model's H x W at (x_min, y_min) of the load_size x load_size resized sample; tgt_labels may be in_labels, NULL for inference
+  virtual void set_input_warp_batch(const uint8_t* body, int N, int Hb, int Wb, const uint8_t* in_labels, const uint8_t* tgt_labels,
+                                    int Hl, int Wl, const double* maps, int nmaps, const float mean[3], const float std_[3],
+                                    int load_size, int x_min, int y_min);
   virtual void get_output(int slot, float* dev_nchw) = 0;
   virtual TView output_view() = 0;              // NHWC view of self.fakes (logical channels: cloth_channels warp / 3 texture)
   virtual int output_channels() const = 0;

@@ -229,6 +229,10 @@ class WarpModel final : public Model {
     G->set_external_slot(cloth.vbase, slot_cloth);
     Var fake_slot = Dx.batch(0, B).slice(0, Ccp);
     build_warp_generator(*G, body, cloth, fake_slot, dropout, Cb, Cc);
+    // the buffers filled from outside and their amax slots as taps: what a hand-over left is read back whole, pad channels included
+    G->taps["body"] = body; G->taps["cloth"] = cloth; G->taps["Dx"] = Dx;
+    auto slot_tap = [](float* slot) { Var v; v.v.p = slot; v.v.N = v.v.H = v.v.W = 1; v.v.C = v.v.cs = AMAX_SLOT; v.vbase = slot; return v; };
+    G->taps["slot_body"] = slot_tap(slot_body); G->taps["slot_cloth"] = slot_tap(slot_cloth); G->taps["slot_dx"] = slot_tap(slot_dx);
     if (!arenaG.frozen) arenaG.allocate(c);          // (a sharing model binds the sharer's frozen arena: shapes were checked)
     G->finalize({fake_slot});
     losses = static_cast<float*>(c.alloc(L_COUNT * sizeof(float)));
@@ -300,6 +304,35 @@ class WarpModel final : public Model {
     else if (slot == 2 && is_train) { labels_to_onehot(ctx->s, lab, Dx.batch(B, B).v.slice(0, Ccp), Cc); ce_done_ = false; }
     else throw Error(1, "set_input_labels: slot has no label form");
     refresh_input_slots(slot);
+  }
+  // slots 0-2 from the compact batch: one launch (ops.h warp_batch) instead of the five nchw_to_nhwc of the calls above, then the
+  // three amax passes refresh_input_slots makes for them (the conditional-D buffer's once)
+  void set_input_warp_batch(const uint8_t* body_u8, int N, int Hb, int Wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int Hl, int Wl,
+                            const double* maps, int nmaps, const float mean[3], const float std_[3], int load_size, int x_min,
+                            int y_min) override {
+    if (N != B) throw Error(1, "set_input_warp_batch: shape mismatch with the model's batch");
+    if (Cb != 3) throw Error(1, "set_input_warp_batch: the body is an RGB image here; this model has " + std::to_string(Cb) + " body channels");
+    if (is_train && !tgt_labels) throw Error(1, "set_input_warp_batch: a training model needs the target label maps");
+    WarpBatchArgs a;
+    a.body = body_u8; a.Hb = Hb; a.Wb = Wb; a.in_labels = in_labels; a.Hl = Hl; a.Wl = Wl; a.maps = maps; a.nmaps = nmaps;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std_[c]; }
+    a.Ls = load_size; a.x_min = x_min; a.y_min = y_min; a.C = Cc;
+    a.in_cloth = cloth.v.slice(0, Ccp);
+    a.body_out[0] = body.v.slice(0, Cbp);
+    a.body_out[1] = Dx.batch(0, B).v.slice(Ccp, Cbp);
+    a.nbody = 2;
+    if (is_train) {                 // (an inference model has no target half: nothing of a target is read or written)
+      a.body_out[2] = Dx.batch(B, B).v.slice(Ccp, Cbp);
+      a.nbody = 3;
+      a.tgt_labels = tgt_labels;
+      a.tgt_cloth = Dx.batch(B, B).v.slice(0, Ccp);
+    }
+    warp_batch(ctx->s, a);
+    ce_done_ = false;               // an early CE term was taken against the old targets: backward_G takes it again
+    Stream& s = ctx->s;
+    tensor_amax(s, body.v, slot_body);
+    tensor_amax(s, cloth.v, slot_cloth);
+    tensor_amax(s, Dx.v, slot_dx, 1.0f);
   }
   void get_output(int slot, float* dst) override {
     if (slot != 0) throw Error(1, "get_output: unknown slot");

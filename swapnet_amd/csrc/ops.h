@@ -1,7 +1,7 @@
 // swapnet_amd -- device op launchers.  The engine (engine.cpp) is written against this
 // header only.  The product implementation is the set of HIP translation units in this
 // directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, batch_norm.hip, losses.hip, optim.hip, gather.hip,
-// texture_batch.hip).
+// texture_batch.hip, warp_batch.hip).
 // tests/hostsim/hostsim_ops.cpp implements the same signatures with plain loops so that
 // the engine's graph / backward / packing logic can be checked in CI without a GPU; it is
 // never part of the shipped library.
@@ -429,6 +429,53 @@ inline void texture_batch_check(const TextureBatchArgs& a) {
   if (a.tgt_tex.p && (!tileable(a.tgt_tex) || a.tgt_tex.C != 4 || !same(a.tgt_tex))) throw Error(1, "texture_batch tgt_tex: view mismatch");
   for (int k = 0; k < a.ncloth; ++k)
     if (!tileable(a.cloth[k]) || a.cloth[k].C != round_up(a.C, 4) || !same(a.cloth[k])) throw Error(1, "texture_batch cloth: view mismatch");
+}
+
+// ---- warp batch hand-over (warp_batch.hip) ------------------------------------------------------------------------------------
+// What WarpDataset.__getitem__ (datasets/warp_dataset.py:139-183) computes per sample on the host, for a whole batch in ONE launch,
+// from the compact form: the decoded uint8 HWC body image (not resized), the uint8 input and target label maps and the per-channel
+// map table of affine_gather (B * C chains of nmaps rows {kind, c0..c7}).  With (y, x) a pixel of the H x W crop window at
+// (y_min, x_min) of the Ls x Ls resized sample, sy = y_min + y, sx = x_min + x, and nearest(d) = min(int(floorf(d * (float(in) / Ls))),
+// in - 1) (torch's nearest rule):
+//   tgt_cloth[b,y,x,:] = one-hot of tgt_labels[b, nearest(sy), nearest(sx)]; label 0 and labels >= C give the all-zero vector
+//   in_cloth[b,y,x,c]  = 1 if channel c's chain, walked backwards from (nearest(sy), nearest(sx)) exactly as affine_gather walks it
+//                        (bounds Wl, Hl), stays inside and ends on a pixel whose in_labels value is c, c != 0; else 0
+//                        (per_channel_transform of the one-hot map, F.interpolate nearest, crop -- the one-hot map never exists)
+//   body[k][b,y,x,c]   = bilinear sample (align_corners False, torch's formula, below) of the texels
+//                        (float(byte) / 255 - mean[c]) / std[c] of the Hb x Wb image at (sy, sx) of its Ls x Ls resize
+//                        (ToTensor, Normalize, F.interpolate(size = Ls, mode = "bilinear"), crop)
+//     src = max(scale * (d + 0.5f) - 0.5f, 0), scale = float(in) / Ls;  i0 = min(int(src), in - 1), i1 = i0 + (i0 < in - 1);
+//     l1 = src - i0, l0 = 1 - l1;  v = h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d)
+// all in fp32, one correctly rounded operation per step (no FMA contraction), pad channels of every view written as zero.
+// tgt_labels may be in_labels (--dataset_mode image); tgt_cloth may be empty (inference: nothing of a target is read or written).
+// Every view must be 16-byte tileable (C % 4, cs % 4, aligned base).
+struct WarpBatchArgs {
+  const uint8_t* body = nullptr; int Hb = 0, Wb = 0;                          // (B,Hb,Wb,3)
+  const uint8_t* in_labels = nullptr; const uint8_t* tgt_labels = nullptr; int Hl = 0, Wl = 0;       // (B,Hl,Wl) each
+  const double* maps = nullptr; int nmaps = 0;                                // [B*C][nmaps][9]; nmaps 0: no augmentation
+  float mean[3] = {0.f, 0.f, 0.f}, std[3] = {1.f, 1.f, 1.f}; int Ls = 0, x_min = 0, y_min = 0; int C = 0;   // C = cloth channels
+  TView in_cloth, tgt_cloth;                                                  // C padded to a multiple of 4; tgt_cloth may be empty
+  TView body_out[3]; int nbody = 0;                                           // one to three 4-channel destinations of the body
+};
+void warp_batch(Stream& s, const WarpBatchArgs& a);
+// the argument checks of every warp_batch implementation (the HIP launcher and the host loop of engine.cpp)
+inline void warp_batch_check(const WarpBatchArgs& a) {
+  auto tileable = [](const TView& v) { return v.p && v.C % 4 == 0 && v.cs % 4 == 0 && v.cs >= v.C && !((uintptr_t)v.p & 15); };
+  const TView& t = a.in_cloth;
+  if (!a.body || !a.in_labels) throw Error(1, "warp_batch: NULL argument");
+  if (a.tgt_cloth.p && !a.tgt_labels) throw Error(1, "warp_batch: a target destination but no target label map");
+  if (a.nmaps < 0 || (a.nmaps > 0 && !a.maps)) throw Error(1, "warp_batch: " + std::to_string(a.nmaps) + " maps per channel but a NULL map table");
+  if (t.N < 1 || t.H < 1 || t.W < 1 || a.Hb < 1 || a.Wb < 1 || a.Hl < 1 || a.Wl < 1 || a.Ls < 1) throw Error(1, "warp_batch: empty sizes");
+  if (a.x_min < 0 || a.y_min < 0 || a.x_min > a.Ls - t.W || a.y_min > a.Ls - t.H)
+    throw Error(1, "warp_batch: crop window (" + std::to_string(a.x_min) + ", " + std::to_string(a.y_min) + ") + " + std::to_string(t.W) +
+                       " x " + std::to_string(t.H) + " lies outside the " + std::to_string(a.Ls) + " x " + std::to_string(a.Ls) + " source");
+  if (a.C < 2 || a.C > 64) throw Error(1, "warp_batch: cloth channels in [2,64]");
+  if (a.nbody < 1 || a.nbody > 3) throw Error(1, "warp_batch: one to three body destinations");
+  if (!tileable(t) || t.C != round_up(a.C, 4)) throw Error(1, "warp_batch in_cloth: view not 16-byte tileable with the padded cloth channels");
+  auto same = [&](const TView& v) { return v.N == t.N && v.H == t.H && v.W == t.W; };
+  if (a.tgt_cloth.p && (!tileable(a.tgt_cloth) || a.tgt_cloth.C != t.C || !same(a.tgt_cloth))) throw Error(1, "warp_batch tgt_cloth: view mismatch");
+  for (int k = 0; k < a.nbody; ++k)
+    if (!tileable(a.body_out[k]) || a.body_out[k].C != 4 || !same(a.body_out[k])) throw Error(1, "warp_batch body: view mismatch");
 }
 
 // ---- losses: each writes the plain MEAN loss into *loss_out (device float) and, if a grad

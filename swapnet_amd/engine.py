@@ -355,6 +355,37 @@ class NativeModel:
             self.ctx.consumed(token)
         self._keep = dev
 
+    def set_input_warp_batch(self, batch):
+        """Warp model: bodys, input_cloths and (training) target_cloths from the compact batch dict of
+        datasets.gpu_warp_batch.GpuWarpBatch.collate (uint8 body images and label maps, the per-channel map table) in one device
+        launch.  `input_labels_u8` being the very tensor `target_labels_u8` is (--dataset_mode image) is uploaded once."""
+        tgt_src, in_src = batch["target_labels_u8"], batch["input_labels_u8"]
+        names = ["bodys_u8", "input_labels_u8"] + (["target_labels_u8"] if self.is_train and tgt_src is not in_src else [])
+        dev, tokens = {}, []
+        for name in names:
+            dev[name], token = self.ctx.upload(torch.as_tensor(batch[name]), torch.uint8, key=(id(self), "wb", name))
+            tokens.append(token)
+        body, lab = dev["bodys_u8"], dev["input_labels_u8"]
+        tgt = dev.get("target_labels_u8", lab) if self.is_train else None
+        maps, nmaps = _warp_maps(batch.get("maps"), body.shape[0], self.cloth_channels)
+        if maps is not None:
+            dev["maps"], token = self.ctx.upload(maps, torch.float64, key=(id(self), "wb", "maps"))
+            tokens.append(token)
+        _check_warp_batch(body, lab, tgt)
+        mean, std = batch["norm_stats"]
+        x_min, y_min = batch["crop"][:2]
+        if tuple(batch["crop"][2:]) not in ((), (self.W, self.H)):
+            raise ValueError("warp batch: its crop window is %s (W, H), the model's %s" % (tuple(batch["crop"][2:]), (self.W, self.H)))
+        self._torch_done()
+        self.lib.call("swn_model_set_input_warp_batch", self.handle, _C.ptr(body), body.shape[0], body.shape[1], body.shape[2], _C.ptr(lab),
+                      _C.ptr(tgt) if tgt is not None else None, lab.shape[1], lab.shape[2],
+                      _C.ptr(dev["maps"]) if maps is not None else None, nmaps, (C.c_float * 3)(*mean), (C.c_float * 3)(*std),
+                      int(batch["load_size"]), int(x_min), int(y_min))
+        self._sync_if_needed()
+        for token in tokens:
+            self.ctx.consumed(token)
+        self._keep = list(dev.values())
+
     def forward(self, training=False, seed=0):
         self.lib.call("swn_model_forward", self.handle, int(training), C.c_uint64(seed))
 
@@ -692,6 +723,52 @@ def op_resample(ctx, op, a, b=None, factor=2, accumulate=False, old=None, views=
     ctx.lib.call("swn_op_resample", ctx.handle, int(op), _C.ptr(ad), _C.ptr(bd), n, c, h, w, f, int(bool(accumulate)), lp,
                  _C.ptr(out), _C.ptr(slot), _C.ptr(pat), _C.ptr(buf))
     return out, slot, pat, buf
+
+
+def _warp_maps(maps, b, cloth_channels):
+    """The map table of a warp batch as a (b * cloth_channels, nmaps, 9) float64 tensor and nmaps; (None, 0) without augmentation."""
+    if maps is None:
+        return None, 0
+    maps = torch.as_tensor(maps)
+    if maps.numel() == 0:
+        return None, 0
+    if maps.dim() != 4 or tuple(maps.shape[:2]) != (b, cloth_channels) or maps.shape[3] != 9:
+        raise ValueError("warp batch: maps must be (B, cloth_channels, nmaps, 9) = (%d, %d, nmaps, 9), got %s"
+                         % (b, cloth_channels, tuple(maps.shape)))
+    return maps.to(torch.float64).reshape(b * cloth_channels, maps.shape[2], 9).contiguous(), int(maps.shape[2])
+
+
+def _check_warp_batch(body, lab, tgt):
+    if body.dim() != 4 or lab.dim() != 3 or (tgt is not None and tgt.dim() != 3):
+        raise ValueError("warp batch: bodys_u8 (B,Hb,Wb,Cb), input_labels_u8 and target_labels_u8 (B,Hl,Wl)")
+    if body.shape[3] != 3:
+        raise ValueError("warp batch: the body is an RGB image (B,Hb,Wb,3), got %d channels" % body.shape[3])
+    if lab.shape[0] != body.shape[0] or (tgt is not None and tuple(tgt.shape) != tuple(lab.shape)):
+        raise ValueError("warp batch: the label maps must share one (B,Hl,Wl) and the bodies' batch size")
+
+
+def op_warp_batch(ctx, bodys_u8, input_labels_u8, target_labels_u8, maps, mean, std, load_size, x_min, y_min, height, width,
+                  cloth_channels=19):
+    """WarpDataset.__getitem__ for a batch through swn_op_warp_batch: (bodys, input_cloths, target_cloths) on the context's device,
+    NCHW float32, from uint8 HWC body images (B,Hb,Wb,3), uint8 label maps (B,Hl,Wl) and the (B, cloth_channels, nmaps, 9) map
+    table (None: no augmentation).  target_labels_u8 None: no targets (target_cloths is None)."""
+    u8 = lambda t: torch.as_tensor(t).to(device=ctx.device, dtype=torch.uint8).contiguous()
+    body, lab = u8(bodys_u8), u8(input_labels_u8)
+    tgt = None if target_labels_u8 is None else (lab if target_labels_u8 is input_labels_u8 else u8(target_labels_u8))
+    _check_warp_batch(body, lab, tgt)
+    b = body.shape[0]
+    maps, nmaps = _warp_maps(maps, b, cloth_channels)
+    md = None if maps is None else maps.to(ctx.device)
+    bodys = torch.empty((b, 3, height, width), dtype=torch.float32, device=ctx.device)
+    inputs = torch.empty((b, cloth_channels, height, width), dtype=torch.float32, device=ctx.device)
+    targets = None if tgt is None else torch.empty_like(inputs)
+    if ctx.owns_stream:                     # (the uploads above ran on torch's stream)
+        torch.cuda.current_stream(ctx.device).synchronize()
+    ctx.lib.call("swn_op_warp_batch", ctx.handle, _C.ptr(body), b, body.shape[1], body.shape[2], _C.ptr(lab),
+                 _C.ptr(tgt) if tgt is not None else None, lab.shape[1], lab.shape[2], _C.ptr(md) if md is not None else None, nmaps,
+                 (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(load_size), int(x_min), int(y_min), int(height), int(width),
+                 int(cloth_channels), _C.ptr(bodys), _C.ptr(inputs), _C.ptr(targets) if targets is not None else None)
+    return bodys, inputs, targets
 
 
 def op_norm_act_bwd2(ctx, x, gy, u, act=1):

@@ -49,9 +49,40 @@ class WarpModel(BaseGAN):
     def get_D_inchannels(self):
         return self.cloth_channels + self.body_channels
 
+    # self.bodys / self.inputs / self.targets: plain attributes on the float hand-over; after a compact batch they are materialised
+    # from it on first use (compute_visuals), never on the training path
+    def _lazy(name):
+        def get(self):
+            if getattr(self, "_" + name, None) is None and getattr(self, "_compact", None) is not None:
+                from ..datasets.gpu_warp_batch import expand_batch
+                ref = expand_batch(self.backend.ctx, self._compact, self.cloth_channels, targets=self.is_train)
+                self._bodys, self._inputs, self._targets = ref["bodys"], ref["input_cloths"], ref.get("target_cloths")
+            return getattr(self, "_" + name)
+
+        def set(self, v):
+            setattr(self, "_" + name, v)
+        return property(get, set)
+
+    bodys, inputs, targets = _lazy("bodys"), _lazy("inputs"), _lazy("targets")
+    del _lazy
+
+    def _set_input_compact(self, input):
+        """The compact batch of datasets.gpu_warp_batch.GpuWarpBatch.collate: every slot in one device launch."""
+        B = input["bodys_u8"].shape[0]
+        _, _, W, H = input["crop"]
+        m = self.backend.ensure(B, H, W)
+        m.set_input_warp_batch(input)
+        self._compact = input
+        self.bodys = self.inputs = self.targets = None
+        self.image_paths = tuple(zip(input["cloth_paths"], input["body_paths"]))
+        self._fakes = None
+
     def set_input(self, input):
         """warp_model.py:99-104.  The three tensors go straight into the library's NHWC buffers
         (the conditioned D input is assembled there, never concatenated)."""
+        if "bodys_u8" in input:
+            return self._set_input_compact(input)
+        self._compact = None
         self.bodys, self.inputs = input["bodys"], input["input_cloths"]
         B, _, H, W = self.bodys.shape
         m = self.backend.ensure(B, H, W)
