@@ -78,7 +78,9 @@ int swn_ctx_set_patchgan_layers(swn_ctx* ctx, int n_layers);
  * parallelism the statistics stay local to each rank (torch DDP's default).
  * Not implemented (the library's "not implemented" error): texture models under kind != 0 (the flag also selects the norm layer
  * of the texture stage's U-Net generator, modules/swapnet_modules.py:176-187, which exists under InstanceNorm only); the
- * gradient-penalty modes under kind != 0; kind 1 on the CI simulator (HIP kernels only). */
+ * gradient-penalty modes under kind != 0; kind 1 on the CI simulator (HIP kernels only).
+ * The flag does not reach the generator (net 0): the only generator with BatchNorm sites is the texture stage's unet_128
+ * (swn_texture_model_create_netG), which has them under kind 0 -- and, as a texture model, refuses any other kind. */
 int swn_ctx_set_patchgan_norm(swn_ctx* ctx, int kind);
 int swn_ctx_sync(swn_ctx* ctx);
 int swn_ctx_bytes_allocated(swn_ctx* ctx, size_t* out);
@@ -135,6 +137,19 @@ int swn_warp_model_create_ex(swn_ctx* ctx, int batch, int height, int width, int
                              int body_channels, int cloth_channels, swn_model** out);
 int swn_texture_model_create_ex(swn_ctx* ctx, int batch, int height, int width, int is_train, int num_roi,
                                 int cloth_channels, swn_model** out);
+/* The texture model with the reference's --netG choice (models/texture_model.py define_G).  netG 0 = swapnet, the ROI-pooled
+ * TextureModule: identical to swn_texture_model_create_ex.  netG 1 = unet_128, the plain pix2pix U-Net baseline (Isola et al.
+ * 2017) UnetGenerator(3, 3, num_downs 7, ngf 64, BatchNorm2d, use_dropout = True) called on the input textures alone: no ROIs and
+ * no cloth input reach the generator (slots 1 and 2 are still staged; the cloths condition the discriminator), against the same
+ * PatchGAN and losses.  Its state dict (net 0) has the prefix `model`: 15 conv tensors (no conv carries a bias except the outermost
+ * ConvTranspose2d, model.model.3.bias), weight / bias of 11 BatchNorm sites as parameters and their running_mean / running_var /
+ * num_batches_tracked as buffers (swn_model_buffer_*), 70 keys.  Dropout(0.5) follows the upnorm of the two inner ngf*8 blocks.
+ * swn_model_forward(training): batch statistics, one running update per call and dropout -- or, training = 0, the running
+ * buffers, nothing updated, no dropout; a backward pass through an eval-mode forward is refused.  Under data parallelism the
+ * statistics stay local to each rank, as the discriminator's do.  height = width in {128, 256}.
+ * Not implemented: netG 1 on the CI simulator (HIP kernels only), and as the texture stage of swn_pipeline_create. */
+int swn_texture_model_create_netG(swn_ctx* ctx, int batch, int height, int width, int is_train, int num_roi,
+                                  int cloth_channels, int netG, swn_model** out);
 /* A second model on the SAME training state: it uses `sharer`'s parameter arenas (weights, gradients, both Adam moments, step
  * counters -- per network one flat buffer each) and owns only its activations and derived operands.  For the reference's loops
  * that is the model of another batch size: the last, smaller batch of an epoch (train.py:62-64 with drop_last off) or the batch-1
@@ -223,7 +238,8 @@ int swn_model_get_tap_grad(swn_model* m, int net, const char* name, float* dev_n
 
 /* nn.Dropout sites of the generator in forward order (WarpModule: body_down4, cloth_down5, cloth_down6 and the
  * four ResidualBlocks, modules/swapnet_modules.py:37,46-47,58 / modules/layers.py:22-23,136; pix2pix U-Net:
- * the three inner ngf*8 blocks, modules/pix2pix_modules.py:251-252).  swn_model_dropout_mask writes the factor
+ * the three inner ngf*8 blocks, modules/pix2pix_modules.py:251-252; the unet_128 generator: the two inner ngf*8 blocks,
+ * where the mask is applied by the BatchNorm apply pass).  swn_model_dropout_mask writes the factor
  * (0 or 1/(1-p)) that a training-mode forward AND backward with `dropout_seed` apply at `site`, as an NCHW
  * tensor of `shape` (channel count = the padded channel count of the layer).  dst may be NULL to query the
  * shape.  Diagnostic: lets a parity test replay the exact masks in the CPU oracle. */
@@ -246,6 +262,7 @@ int swn_model_dropout_mask(swn_model* m, int net, int site, uint64_t dropout_see
  * datasets/data_utils.py:311-343) kept in HBM: warp forward -> argmax label map -> one-hot into the texture model's
  * cloth inputs -> texture forward.  Inputs are staged with swn_model_set_input on the two models beforehand (warp
  * slots 0,1; texture slots 0,1 -- texture slot 2 is produced here); the result is the texture model's output.
+ * A texture model created with netG = unet_128 is refused ("not implemented"): that generator has no cloth input to hand over.
  * use_graph != 0: the first call runs eagerly and captures the sequence into a hipGraph, later calls replay it
  * (*graph_replayed = 1).  Both models must be inference models (is_train = 0) of one context and one (B,H,W). */
 typedef struct swn_pipeline swn_pipeline;
@@ -274,8 +291,9 @@ int swn_model_discriminate(swn_model* m, const float* x_nchw, float* pred_nchw);
  * with the running buffers.  No effect under --norm instance / none.  The training step itself always runs in train mode. */
 int swn_model_set_discriminate_mode(swn_model* m, int training);
 /* state_dict() buffers of a network (torch.nn.BatchNorm2d's running_mean, running_var, num_batches_tracked under the keys of
- * modules/discriminators.py:119,127,160: model.K.* / net.3.*): neither optimised nor exchanged.  Only the discriminator (net 1)
- * under swn_ctx_set_patchgan_norm(ctx, 1) has any.  info: numel elements of fp32, or one int64 when *is_int64.  set / get copy
+ * modules/discriminators.py:119,127,160: model.K.* / net.3.*): neither optimised nor exchanged.  The discriminator (net 1) has
+ * them under swn_ctx_set_patchgan_norm(ctx, 1); the generator (net 0) of a texture model created with netG = unet_128 has 33
+ * (11 sites, keys model.model.1.model.2.* ...); no other network has any.  info: numel elements of fp32, or one int64 when *is_int64.  set / get copy
  * between DEVICE pointers of that type.  Models sharing arenas (swn_model_create_shared) share the buffers. */
 int swn_model_buffer_count(swn_model* m, int net, int* out);
 int swn_model_buffer_info(swn_model* m, int net, int index, char* name, int name_len, int* numel, int* is_int64);
@@ -403,6 +421,14 @@ int swn_op_batch_norm_act(swn_ctx* ctx, const float* x, int n, int c, int h, int
                           int64_t* num_batches_tracked, float* y, float* save_stats);
 int swn_op_batch_norm_act_bwd(swn_ctx* ctx, const float* x, const float* dy, int n, int c, int h, int w, int groups, int act,
                               const float* weight, const float* bias, float* dx, float* dweight, float* dbias);
+/* BatchNorm2d -> [act] -> nn.Dropout(p) in TRAINING mode as ONE op (the upnorm -> Dropout sites of the pix2pix U-Net), one group,
+ * no running buffers: y, the keep/scale mask it used (0 or 1/(1-p); optional, p > 0 only) and, when dy and dx are given (they go
+ * together), dx and optionally dweight / dbias computed with the same mask: a dropped element adds nothing to any of them.
+ * p = 0 launches the kernels of swn_op_batch_norm_act / _bwd and gives their results bit for bit.  NCHW fp32, C % 4 == 0.
+ * HIP kernels only: the CI simulator returns the library's "not implemented" error. */
+int swn_op_batch_norm_act_dropout(swn_ctx* ctx, const float* x, const float* dy, int n, int c, int h, int w, int act, float p,
+                                  uint64_t seed, const float* weight, const float* bias, float* y, float* mask, float* dx,
+                                  float* dweight, float* dbias);
 /* The forward (what 0) or backward (what 1) pass of the layer behind swn_op_instance_norm_act (kind 0; modules/__init__.py:66-69) or
  * swn_op_batch_norm_act (kind 1, training mode, weight 1, bias 0; modules/__init__.py:62-65) timed with HIP events on the
  * context's stream: `warmup` untimed runs, then `iters` timed ones back to back on the same buffers, ms_out[i] (HOST floats) = the

@@ -50,6 +50,7 @@ _PROTOS = {
     "swn_texture_model_create": ([_vp, _i, _i, _i, _i, _i, C.POINTER(_vp)], _i),
     "swn_warp_model_create_ex": ([_vp, _i, _i, _i, _i, _f, _i, _i, C.POINTER(_vp)], _i),
     "swn_texture_model_create_ex": ([_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)], _i),
+    "swn_texture_model_create_netG": ([_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)], _i),
     "swn_model_create_shared": ([_vp, _i, _i, _i, C.POINTER(_vp)], _i),
     "swn_model_destroy": ([_vp], _i),
     "swn_model_set_hyper": ([_vp, C.POINTER(SwnHyper)], _i),
@@ -110,6 +111,7 @@ _PROTOS = {
     "swn_op_instance_norm_act_bwd": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _fp], _i),
     "swn_op_batch_norm_act": ([_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _vp, _fp, _fp], _i),
     "swn_op_batch_norm_act_bwd": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp], _i),
+    "swn_op_batch_norm_act_dropout": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _f, C.c_uint64, _fp, _fp, _fp, _fp, _fp, _fp, _fp], _i),
     "swn_op_norm_act_time": ([_vp, _i, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float)], _i),
     "swn_op_affine_gather": ([_vp, _fp, _fp, _i, _i, _i, _i, _vp, _i], _i),
     "swn_op_texture_batch": ([_vp, _vp, _i, _i, _i, _vp, _i, _i, _fp, _i, _fp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i,

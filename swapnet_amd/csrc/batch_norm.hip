@@ -4,6 +4,8 @@
 // once on the fakes and once on the targets, run here as one 2B batch.  Same split as norm_act.hip: per (image, pixel chunk, channel)
 // partial sums in fp64 -> a finalize kernel that reduces a group's partials in a fixed order -> one apply pass with 16-byte accesses.
 // No floating-point atomics: two runs on the same inputs are bit-identical.
+// Optionally Dropout(p) follows in the same apply pass, forward and backward (the upnorm -> Dropout sites of the pix2pix U-Net,
+// Isola et al. 2017): separate instantiations, so a call without dropout launches the kernels it always did.
 // Reference: modules/__init__.py:62-65 (BatchNorm2d(affine=True, track_running_stats=True)), modules/discriminators.py:113-128,160-162.
 #include <algorithm>
 
@@ -39,11 +41,25 @@ struct BNp {
   int N, HW, C, nchunk, chunk, groups, act;
   float* amax_out;
 };
+// Dropout behind the activation (conventions of norm_act.hip): factor drop_scale(seed, element index, p).  Only the DROP
+// instantiations take these fields: the kernels of a call without dropout keep BNp, their argument block, as it was.
+struct BNpDrop : BNp {
+  float drop_p;
+  uint64_t seed;
+  const uint64_t* seed_base;      // captured step: the step seed lives in device memory; seed = *seed_base * 0x9E3779B1 + salt
+  uint64_t salt;
+};
+template <int DROP> struct BNArg { typedef BNp type; };
+template <> struct BNArg<1> { typedef BNpDrop type; };
+__device__ __forceinline__ uint64_t bn_seed(const BNp&) { return 0; }
+__device__ __forceinline__ uint64_t bn_seed(const BNpDrop& p) { return p.seed_base ? *p.seed_base * 0x9E3779B1ull + p.salt : p.seed; }
 
 // partial sums over a pixel chunk of one image: MODE 0 -> (sum x, sum x^2); MODE 1 -> (sum dy', sum dy' * xh), dy' = dy * act'(z)
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_partial_kernel(BNp p) {
+// DROP (MODE 1 only): dy is first multiplied by the forward's keep/scale factor, so a dropped element adds 0 to both sums
+template <int MODE, int DROP = 0>
+__global__ __launch_bounds__(256) void bn_partial_kernel(typename BNArg<DROP>::type p) {
   __shared__ double red[256 * 8];
+  const uint64_t drop_seed_v = bn_seed(p);
   const int C4 = p.C >> 2;
   const int rows = 256 / C4;
   const int t = threadIdx.x, tx = t % C4, ty = t / C4;
@@ -74,7 +90,9 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(BNp p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float z = xa[j] * sc[j] + sh[j];                        // the forward's value (selects the activation branch)
-          const float d = ga[j] * bn_act_grad(z, p.act);
+          float gd = ga[j];
+          if constexpr (DROP != 0) gd *= drop_scale(drop_seed_v, e * p.C + tx * 4 + j, p.drop_p);
+          const float d = gd * bn_act_grad(z, p.act);
           s[j] += d; ss[j] += (double)d * (((double)xa[j] - (double)mean[j]) * (double)rstd[j]);
         }
       }
@@ -152,7 +170,10 @@ __global__ void bn_fold_running_kernel(BNp p) {
   p.fold[p.C + c] = (float)((double)p.beta[c] - (double)p.running_mean[c] * (double)scale);
 }
 
-__global__ __launch_bounds__(256) void bn_apply_kernel(BNp p) {
+// DROP: y = act(x * scale + shift) * keep/scale factor; the amax slot sees the masked values
+template <int DROP>
+__global__ __launch_bounds__(256) void bn_apply_kernel(typename BNArg<DROP>::type p) {
+  const uint64_t drop_seed_v = bn_seed(p);
   const int C4 = p.C >> 2;
   const size_t total = (size_t)p.N * p.HW * C4;
   const int npg = p.N / p.groups;
@@ -164,15 +185,22 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BNp p) {
     const float4 xv = *reinterpret_cast<const float4*>(p.x + e * p.xcs + c);
     const float4 sc = *reinterpret_cast<const float4*>(p.fold + (size_t)g * 2 * p.C + c);
     const float4 sh = *reinterpret_cast<const float4*>(p.fold + ((size_t)g * 2 + 1) * p.C + c);
-    const float4 o4 = make_float4(act_apply(xv.x * sc.x + sh.x, p.act), act_apply(xv.y * sc.y + sh.y, p.act),
-                                  act_apply(xv.z * sc.z + sh.z, p.act), act_apply(xv.w * sc.w + sh.w, p.act));
+    float4 o4 = make_float4(act_apply(xv.x * sc.x + sh.x, p.act), act_apply(xv.y * sc.y + sh.y, p.act),
+                            act_apply(xv.z * sc.z + sh.z, p.act), act_apply(xv.w * sc.w + sh.w, p.act));
+    if constexpr (DROP != 0) {
+      const uint64_t idx = (uint64_t)e * p.C + c;
+      o4.x *= drop_scale(drop_seed_v, idx, p.drop_p); o4.y *= drop_scale(drop_seed_v, idx + 1, p.drop_p);
+      o4.z *= drop_scale(drop_seed_v, idx + 2, p.drop_p); o4.w *= drop_scale(drop_seed_v, idx + 3, p.drop_p);
+    }
     *reinterpret_cast<float4*>(p.y + e * p.ycs + c) = o4;
     am = fmaxf(am, f4amax(o4));
   }
   amax_fold(am, p.amax_out);
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BNp p) {
+template <int DROP>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(typename BNArg<DROP>::type p) {
+  const uint64_t drop_seed_v = bn_seed(p);
   const int C4 = p.C >> 2;
   const size_t total = (size_t)p.N * p.HW * C4;
   const int npg = p.N / p.groups;
@@ -193,7 +221,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BNp p) {
       const size_t gc = (size_t)g * p.C + c + j;
       const float mean = p.stats[gc * 2], rstd = p.stats[gc * 2 + 1];
       const double m1 = p.coef[gc * 2], m2 = p.coef[gc * 2 + 1];
-      const float d = ga[j] * bn_act_grad(xa[j] * sca[j] + sha[j], p.act);
+      float gd = ga[j];
+      if constexpr (DROP != 0) gd *= drop_scale(drop_seed_v, (uint64_t)e * p.C + c + j, p.drop_p);
+      const float d = gd * bn_act_grad(xa[j] * sca[j] + sha[j], p.act);
       // d - mean(d) - xh * mean(d xh) cancels (norm_act.hip norm_act_bwd_apply_kernel): combined in double, the pass is HBM-bound
       o[j] = (float)((double)sca[j] * ((double)d - m1 - (((double)xa[j] - (double)mean) * (double)rstd) * m2));
     }
@@ -242,6 +272,8 @@ void batch_norm_fwd(Stream& s, const BatchNormArgs& a) {
   p.y = a.y.p; p.ycs = a.y.cs; p.gamma = a.gamma; p.beta = a.beta; p.act = a.act;
   p.running_mean = a.running_mean; p.running_var = a.running_var; p.nbt = a.num_batches_tracked;
   p.stats = a.stats; p.fold = a.fold; p.amax_out = a.amax_out;
+  if (a.drop_p < 0.f || a.drop_p >= 1.f) throw Error(1, "batch_norm_fwd: dropout probability must be in [0, 1)");
+  const bool drop = a.training && a.drop_p > 0.f;          // eval mode: no mask
   if (a.training) {
     if (!a.stats) throw Error(1, "batch_norm_fwd: stats buffer required in training mode");
     if ((bool)a.running_mean != (bool)a.running_var) throw Error(1, "batch_norm_fwd: running_mean and running_var go together");
@@ -253,12 +285,14 @@ void batch_norm_fwd(Stream& s, const BatchNormArgs& a) {
       if (a.partial_chunks <= 0 || p.HW % a.partial_chunks) throw Error(1, "batch_norm_fwd: bad partial_chunks");
       p.nchunk = a.partial_chunks; p.chunk = p.HW / a.partial_chunks;
       p.partial = const_cast<double*>(a.partial_in);
-      if (route_on()) route_note("batch_norm_fwd[statistics from the conv epilogue, bn_finalize_kernel, bn_apply_kernel]");
+      if (route_on()) route_note(drop ? "batch_norm_fwd[statistics from the conv epilogue, bn_finalize_kernel, bn_apply_kernel + dropout]"
+                                      : "batch_norm_fwd[statistics from the conv epilogue, bn_finalize_kernel, bn_apply_kernel]");
     } else {
       batch_norm_plan_chunks(p.HW, p.N, p.C, p.nchunk, p.chunk);
       p.partial = reinterpret_cast<double*>(s.ws);
       if ((size_t)p.N * p.nchunk * p.C * 16 > s.ws_bytes) throw Error(1, "batch_norm_fwd: workspace too small");
-      if (route_on()) route_note("batch_norm_fwd[bn_partial_kernel, bn_finalize_kernel, bn_apply_kernel]");
+      if (route_on()) route_note(drop ? "batch_norm_fwd[bn_partial_kernel, bn_finalize_kernel, bn_apply_kernel + dropout]"
+                                      : "batch_norm_fwd[bn_partial_kernel, bn_finalize_kernel, bn_apply_kernel]");
       hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(p.nchunk, p.N), dim3(256), 0, hs(s), p);
     }
     hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(ceil_div(p.C, 16)), dim3(256), 0, hs(s), p);
@@ -267,7 +301,15 @@ void batch_norm_fwd(Stream& s, const BatchNormArgs& a) {
     if (route_on()) route_note("batch_norm_fwd[eval: bn_fold_running_kernel, bn_apply_kernel]");
     hipLaunchKernelGGL(bn_fold_running_kernel, dim3(ceil_div(p.C, 256)), dim3(256), 0, hs(s), p);
   }
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_grid((size_t)p.N * p.HW * (p.C / 4))), dim3(256), 0, hs(s), p);
+  const dim3 agrid(bn_grid((size_t)p.N * p.HW * (p.C / 4)));
+  if (drop) {
+    BNpDrop pd{};
+    static_cast<BNp&>(pd) = p;
+    pd.drop_p = a.drop_p; pd.seed = a.seed; pd.seed_base = a.seed_base; pd.salt = a.salt;
+    hipLaunchKernelGGL(bn_apply_kernel<1>, agrid, dim3(256), 0, hs(s), pd);
+  } else {
+    hipLaunchKernelGGL(bn_apply_kernel<0>, agrid, dim3(256), 0, hs(s), p);
+  }
   check_launch("batch_norm_fwd");
 }
 
@@ -279,16 +321,27 @@ void batch_norm_bwd(Stream& s, const BatchNormBwdArgs& a) {
   p.dy = a.dy.p; p.dycs = a.dy.cs; p.y = a.dx.p; p.ycs = a.dx.cs; p.act = a.act;
   p.stats = const_cast<float*>(a.stats); p.fold = const_cast<float*>(a.fold);
   p.dgamma = a.dgamma; p.dbeta = a.dbeta; p.amax_out = a.amax_out;
+  if (a.drop_p < 0.f || a.drop_p >= 1.f) throw Error(1, "batch_norm_bwd: dropout probability must be in [0, 1)");
+  const bool drop = a.drop_p > 0.f;
   batch_norm_plan_chunks(p.HW, p.N, p.C, p.nchunk, p.chunk);
   p.partial = reinterpret_cast<double*>(s.ws);
   const size_t pbytes = ((size_t)p.N * p.nchunk * p.C * 16 + 255) / 256 * 256;
   p.coef = reinterpret_cast<double*>(s.ws + pbytes);
   if (pbytes + (size_t)p.groups * p.C * 16 > s.ws_bytes) throw Error(1, "batch_norm_bwd: workspace too small");
-  if (route_on()) route_note(a.dgamma ? "batch_norm_bwd[bn_partial_kernel, bn_finalize_kernel, bn_bwd_apply_kernel]"
-                                      : "batch_norm_bwd[bn_partial_kernel, bn_finalize_kernel (no parameter gradients), bn_bwd_apply_kernel]");
-  hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(p.nchunk, p.N), dim3(256), 0, hs(s), p);
+  const dim3 agrid(bn_grid((size_t)p.N * p.HW * (p.C / 4)));
+  if (route_on()) {
+    const std::string pre = drop ? "batch_norm_bwd[dropout: " : "batch_norm_bwd[";
+    route_note((pre + (a.dgamma ? "bn_partial_kernel, bn_finalize_kernel, bn_bwd_apply_kernel]"
+                                : "bn_partial_kernel, bn_finalize_kernel (no parameter gradients), bn_bwd_apply_kernel]")).c_str());
+  }
+  BNpDrop pd{};
+  static_cast<BNp&>(pd) = p;
+  pd.drop_p = a.drop_p; pd.seed = a.seed; pd.seed_base = a.seed_base; pd.salt = a.salt;
+  if (drop) hipLaunchKernelGGL((bn_partial_kernel<1, 1>), dim3(p.nchunk, p.N), dim3(256), 0, hs(s), pd);
+  else hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(p.nchunk, p.N), dim3(256), 0, hs(s), p);
   hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(ceil_div(p.C, 16)), dim3(256), 0, hs(s), p);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_grid((size_t)p.N * p.HW * (p.C / 4))), dim3(256), 0, hs(s), p);
+  if (drop) hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, agrid, dim3(256), 0, hs(s), pd);
+  else hipLaunchKernelGGL(bn_bwd_apply_kernel<0>, agrid, dim3(256), 0, hs(s), p);
   check_launch("batch_norm_bwd");
 }
 

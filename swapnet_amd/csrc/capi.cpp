@@ -29,6 +29,7 @@ struct swn_model {
   std::shared_ptr<Model> m;
   // what it was created with (a sharing model is created like its sharer, at another batch size)
   int kind = 0, is_train = 1, num_roi = 12, body_channels = 3, cloth_channels = 19, patchgan_layers = 3, patchgan_norm = 0;
+  int netG = 0;                     // texture models: --netG (0 swapnet, 1 unet_128)
   float dropout = 0.5f;
 };
 struct swn_pipeline {
@@ -158,17 +159,21 @@ int swn_warp_model_create(swn_ctx* ctx, int batch, int height, int width, int is
                           swn_model** out) {
   return swn_warp_model_create_ex(ctx, batch, height, width, is_train, dropout, 3, 19, out);
 }
-int swn_texture_model_create_ex(swn_ctx* ctx, int batch, int height, int width, int is_train, int num_roi,
-                                int cloth_channels, swn_model** out) {
+int swn_texture_model_create_netG(swn_ctx* ctx, int batch, int height, int width, int is_train, int num_roi,
+                                  int cloth_channels, int netG, swn_model** out) {
   return guard([&] {
     REQUIRE(ctx && out, "NULL argument");
     auto h = std::make_unique<swn_model>();
     h->keep = ctx->box;
-    h->m.reset(create_texture_model(*ctx->c, batch, height, width, is_train != 0, num_roi, cloth_channels));
+    h->m.reset(create_texture_model(*ctx->c, batch, height, width, is_train != 0, num_roi, cloth_channels, nullptr, netG));
     h->kind = 1; h->is_train = is_train != 0; h->num_roi = num_roi; h->cloth_channels = cloth_channels;
-    h->patchgan_layers = ctx->c->patchgan_layers;
+    h->patchgan_layers = ctx->c->patchgan_layers; h->netG = netG;
     *out = h.release();
   });
+}
+int swn_texture_model_create_ex(swn_ctx* ctx, int batch, int height, int width, int is_train, int num_roi,
+                                int cloth_channels, swn_model** out) {
+  return swn_texture_model_create_netG(ctx, batch, height, width, is_train, num_roi, cloth_channels, NETG_SWAPNET, out);
 }
 int swn_texture_model_create(swn_ctx* ctx, int batch, int height, int width, int is_train, int num_roi,
                              swn_model** out) {
@@ -185,14 +190,14 @@ int swn_model_create_shared(swn_model* sharer, int batch, int height, int width,
     h->sharer = root;
     h->kind = sharer->kind; h->is_train = sharer->is_train; h->dropout = sharer->dropout; h->num_roi = sharer->num_roi;
     h->body_channels = sharer->body_channels; h->cloth_channels = sharer->cloth_channels; h->patchgan_layers = sharer->patchgan_layers;
-    h->patchgan_norm = sharer->patchgan_norm;
+    h->patchgan_norm = sharer->patchgan_norm; h->netG = sharer->netG;
     const int layers_was = c.patchgan_layers, norm_was = c.patchgan_norm;
     c.patchgan_layers = sharer->patchgan_layers; c.patchgan_norm = sharer->patchgan_norm;
     try {
       if (h->kind == 0)
         h->m.reset(create_warp_model(c, batch, height, width, h->is_train != 0, h->dropout, h->body_channels, h->cloth_channels, root.get()));
       else
-        h->m.reset(create_texture_model(c, batch, height, width, h->is_train != 0, h->num_roi, h->cloth_channels, root.get()));
+        h->m.reset(create_texture_model(c, batch, height, width, h->is_train != 0, h->num_roi, h->cloth_channels, root.get(), h->netG));
     } catch (...) { c.patchgan_layers = layers_was; c.patchgan_norm = norm_was; throw; }
     c.patchgan_layers = layers_was; c.patchgan_norm = norm_was;
     h->m->hyper = root->hyper;
@@ -303,11 +308,12 @@ int swn_model_param_get(swn_model* m, int net, int which, const char* name, floa
     else unpack_weight(s, d.ws, a.base(which) + d.off, dst);
   });
 }
-// ---- state-dict buffers: the running statistics of the discriminator's BatchNorm sites -------------------------------------
+// ---- state-dict buffers: the running statistics of the BatchNorm sites of the discriminator (--norm batch) and of the
+// texture stage's unet_128 generator -----------------------------------------------------------------------------------------
 static std::vector<Model::BNSite>& sites_of(swn_model* m, int net) {
   static std::vector<Model::BNSite> none;
   arena_of(m, net);                      // (validates the model and the network)
-  return net == 1 ? m->m->bn_sites() : none;
+  return net == 0 || net == 1 ? m->m->bn_sites(net) : none;
 }
 static const char* const kBufferNames[3] = {"running_mean", "running_var", "num_batches_tracked"};
 static void* find_buffer(swn_model* m, int net, const char* name, size_t* bytes) {
@@ -473,6 +479,9 @@ int swn_model_perceptual(swn_model* m, const float* output, const float* target,
 int swn_pipeline_create(swn_model* warp, swn_model* texture, swn_pipeline** out) {
   return guard([&] {
     REQUIRE(warp && texture && out, "NULL argument");
+    // the two-stage hand-off feeds the texture generator's cloth input, which the plain U-Net does not have
+    REQUIRE(texture->kind != 1 || texture->netG == NETG_SWAPNET,
+            "swn_pipeline_create: a --netG unet_128 texture model is not implemented (the hand-off feeds a cloth input this generator does not have)");
     auto h = std::make_unique<swn_pipeline>();
     h->keep = warp->keep;
     h->p = std::make_unique<Pipeline>(*warp->m, *texture->m);
@@ -831,6 +840,44 @@ int swn_op_batch_norm_act_bwd(swn_ctx* ctx, const float* x, const float* dy, int
     if (dweight) {
       dev_copy(tmp.s, dweight, A.g + A.params[A.index.at("bn.weight")].off, c * sizeof(float));
       dev_copy(tmp.s, dbias, A.g + A.params[A.index.at("bn.bias")].off, c * sizeof(float));
+    }
+    stream_sync(tmp.s);
+  });
+}
+// BatchNorm2d -> [act] -> Dropout(p), training mode, as one call: the fused site of Net::batch_norm_act(..., drop_p)
+int swn_op_batch_norm_act_dropout(swn_ctx* ctx, const float* x, const float* dy, int n, int c, int h, int w, int act, float p,
+                                  uint64_t seed, const float* weight, const float* bias, float* y, float* mask, float* dx,
+                                  float* dweight, float* dbias) {
+  return guard([&] {
+    REQUIRE(ctx && x && y && weight && bias && c % 4 == 0, "bad argument (C must be a multiple of 4)");
+    REQUIRE(p >= 0.f && p < 1.f, "dropout probability must be in [0, 1)");
+    REQUIRE((dy != nullptr) == (dx != nullptr), "dy and dx go together");
+    REQUIRE((dweight != nullptr) == (dbias != nullptr) && (!dweight || dy), "dweight and dbias go together and need dy / dx");
+    REQUIRE(!mask || p > 0.f, "mask requested with p == 0");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Var xv = net.alloc_var(n, h, w, c, true), yv = net.alloc_var(n, h, w, c, true);
+    net.batch_norm_act("bn", xv, yv, act, 1, Net::BNBuffers(), p);
+    A.allocate(tmp);
+    net.finalize({});
+    dev_copy(tmp.s, A.w + A.params[A.index.at("bn.weight")].off, weight, c * sizeof(float));
+    dev_copy(tmp.s, A.w + A.params[A.index.at("bn.bias")].off, bias, c * sizeof(float));
+    net.training = true; net.bn_training = true; net.seed = seed;
+    nchw_to_nhwc(tmp.s, x, n, c, h, w, xv.v);
+    net.forward();
+    nhwc_to_nchw(tmp.s, yv.v, y, c);
+    if (mask) {
+      const Net::DropSite& d = net.drop_sites.at(0);
+      dropout_mask(tmp.s, d.N, d.H, d.W, d.C, d.p, Net::drop_seed(seed, d.salt), mask);
+    }
+    if (dy) {
+      nchw_to_nhwc(tmp.s, dy, n, c, h, w, yv.g);
+      net.backward(dweight != nullptr, true);
+      nhwc_to_nchw(tmp.s, xv.g, dx, c);
+      if (dweight) {
+        dev_copy(tmp.s, dweight, A.g + A.params[A.index.at("bn.weight")].off, c * sizeof(float));
+        dev_copy(tmp.s, dbias, A.g + A.params[A.index.at("bn.bias")].off, c * sizeof(float));
+      }
     }
     stream_sync(tmp.s);
   });

@@ -1138,10 +1138,13 @@ void Net::norm_act(const Var& raw, const Var& y, bool norm, int actf, float drop
 }
 
 // ---- BatchNorm2d -> act (batch_norm.hip) -------------------------------------------------
-void Net::batch_norm_act(const std::string& name, const Var& raw, const Var& y, int actf, int groups, const BNBuffers& run) {
+void Net::batch_norm_act(const std::string& name, const Var& raw, const Var& y, int actf, int groups, const BNBuffers& run,
+                         float drop_p) {
   auto op = std::make_unique<Op>();
   op->label = "batch_norm_act";
   const int C = raw.v.C;
+  const uint64_t salt = ops.size() + 1;
+  if (drop_p > 0.f) drop_sites.push_back({salt, raw.v.N, raw.v.H, raw.v.W, raw.v.C, drop_p});
   const size_t goff = arena.params[arena.add_bias(name + ".weight", C)].off;
   const size_t boff = arena.params[arena.add_bias(name + ".bias", C)].off;
   op->param_off = goff;
@@ -1166,6 +1169,9 @@ void Net::batch_norm_act(const std::string& name, const Var& raw, const Var& y, 
     a.stats = stats; a.fold = fold; a.groups = groups; a.act = actf; a.training = n.bn_training ? 1 : 0;
     a.amax_out = n.amax + ySlot;
     if (n.bn_training) { a.partial_in = partial_in; a.partial_chunks = partial_chunks; }
+    if (drop_p > 0.f && n.training && n.bn_training) {
+      a.drop_p = drop_p; a.seed = Net::drop_seed(n.seed, salt); a.seed_base = n.seed_dev; a.salt = salt;
+    }
     batch_norm_fwd(n.ctx.s, a);
   };
   op->bwd = [=](Net& n, Op&, bool wgrad, bool) {
@@ -1174,6 +1180,9 @@ void Net::batch_norm_act(const std::string& name, const Var& raw, const Var& y, 
     BatchNormBwdArgs b;
     b.dy = yg; b.x = rv; b.stats = stats; b.fold = fold; b.dx = rg; b.groups = groups; b.act = actf;
     if (wgrad) { b.dgamma = n.arena.g + goff; b.dbeta = n.arena.g + boff; }
+    if (drop_p > 0.f && n.training) {
+      b.drop_p = drop_p; b.seed = Net::drop_seed(n.seed, salt); b.seed_base = n.seed_dev; b.salt = salt;
+    }
     b.amax_out = n.amax + gSlot;
     batch_norm_bwd(n.ctx.s, b);
   };
@@ -1485,15 +1494,15 @@ void Model::optimizer_step(int net) {
   A.version += 1;
 }
 
-Net::BNBuffers Model::bn_site(const std::string& name, int C) {
-  for (BNSite& s : bn_sites())
+Net::BNBuffers Model::bn_site(const std::string& name, int C, int net) {
+  for (BNSite& s : bn_sites(net))
     if (s.name == name) {
       if (s.C != C) throw Error(1, "BatchNorm site " + name + ": channel count differs from the arena owner's");
       return s.run;
     }
   if (share_) throw Error(1, "shared model: the arena's owner has no BatchNorm site " + name);
-  bn_sites_.emplace_back();
-  BNSite& s = bn_sites_.back();
+  bn_sites_[net].emplace_back();
+  BNSite& s = bn_sites_[net].back();
   s.name = name; s.C = C; s.ones.assign(C, 1.f);
   float* buf = static_cast<float*>(ctx->alloc((size_t)2 * C * sizeof(float) + 16));      // zero-filled: mean 0, count 0
   s.run = Net::BNBuffers{buf, buf + C, reinterpret_cast<long long*>(buf + 2 * C)};

@@ -65,7 +65,8 @@ struct Ctx {
   // discriminator of every WARP model created on this context afterwards -- 0 instance (the reference's default), 1 batch
   // (BatchNorm2d, affine, running statistics: Net::batch_norm_act), 2 none (identity).  Under 1 and 2 the inner convs have no bias
   // (use_bias is true only under InstanceNorm2d, :104-107,151-154).  The texture stage's generator takes the same flag in the
-  // reference and has no BatchNorm form here yet: texture models refuse a non-instance kind.
+  // reference; its generators exist under one norm layer each (TextureModule: instance; --netG unet_128: batch, whatever this says),
+  // so texture models refuse a non-instance kind.
   int patchgan_norm = 0;
   explicit Ctx(void* stream, size_t ws_bytes);
   explicit Ctx(const Stream& shared);      // borrows stream + workspace of another context
@@ -257,9 +258,12 @@ class Net {
   // optimizer update, weight decay, the gradient exchange and the state dict cover them like any bias); the running statistics
   // belong to the caller, who hands the same BNBuffers to every net that shares the site.  groups: see ops.h.  The op follows
   // bn_training (torch's train() / eval()); its backward skips d gamma / d beta when the pass takes no weight gradients.
+  // drop_p > 0: Dropout(p) follows in the same apply pass (ops.h BatchNormArgs::drop_p) and the site is registered in drop_sites
+  // exactly as norm_act registers its own; the mask is applied when the net is `training` AND in bn_training (eval: none).
   struct BNBuffers { float* mean = nullptr; float* var = nullptr; long long* count = nullptr; };
   bool bn_training = true;
-  void batch_norm_act(const std::string& name, const Var& raw, const Var& y, int act, int groups, const BNBuffers& run);
+  void batch_norm_act(const std::string& name, const Var& raw, const Var& y, int act, int groups, const BNBuffers& run,
+                      float drop_p = 0.f);
   void act(const Var& x, const Var& y, int act);
   void upsample(const Var& x, const Var& y, int factor);
   void maxpool(const Var& x, const Var& y);
@@ -319,6 +323,12 @@ Var build_patchgan(Net& net, const Var& x, int n_layers, const std::vector<int32
                    const PatchganNorm& norm = PatchganNorm());
 void build_texture_generator(Net& net, const Var& tex, const float* rois_dev, int num_roi, const Var& cloth_cat,
                              const Var& unet_in, const Var& out, int img_size, int cloth_channels = 19);
+// --netG unet_128: the plain pix2pix U-Net (Isola et al. 2017) under BatchNorm2d, UnetGenerator(3, 3, num_downs 7, ngf 64,
+// use_dropout) on the 3-channel texture buffer -- no ROIs, no cloth input.  site(name, C): the running buffers of a norm site
+// (the model: nets bound to one arena share them).  H = W in {128, 256}.
+void build_unet128_generator(Net& net, const Var& tex, const Var& out,
+                             const std::function<Net::BNBuffers(const std::string& name, int C)>& site);
+enum TextureNetG : int { NETG_SWAPNET = 0, NETG_UNET128 = 1 };
 // img: the image buffer (>= 4 channels, RGB in the first three; 16 channels put conv1_1 on the ring kernel) -- its gradient, if any,
 // is formed for the first 4 channels only
 std::vector<Var> build_vgg16_slices(Net& net, const Var& img);
@@ -497,14 +507,17 @@ class Model {
  public:
   int patchgan_layers() const { return d_layers_; }
   int patchgan_norm() const { return d_norm_; }
-  // Running statistics of the discriminator's BatchNorm sites (state-dict buffers `name`.running_mean / .running_var /
+  // Running statistics of the BatchNorm sites of a network (state-dict buffers `name`.running_mean / .running_var /
   // .num_batches_tracked): neither optimised nor exchanged, so they live outside the parameter arena.  Owned by the model that
-  // owns the arena; D2 (2B images, two groups), D1 and the discriminate() instance of it and of every sharing model update the same
-  // buffers -- per step in the reference's order: fake run, real run, then the fakes through the updated D.
+  // owns the arena.  net 1, the discriminator: D2 (2B images, two groups), D1 and the discriminate() instance of it and of every
+  // sharing model update the same buffers -- per step in the reference's order: fake run, real run, then the fakes through the
+  // updated D.  net 0, the generator (texture stage, --netG unet_128): one update per training-mode forward; the generators of all
+  // sharing models update the same buffers.
   struct BNSite { std::string name; int C = 0; Net::BNBuffers run; std::vector<float> ones; };
-  std::vector<BNSite> bn_sites_;  // the arena owner's
-  std::vector<BNSite>& bn_sites() { return share_ ? share_->bn_sites() : bn_sites_; }
-  Net::BNBuffers bn_site(const std::string& name, int C);      // finds the site; the arena's owner creates it (mean 0, var 1, count 0)
+  std::vector<BNSite> bn_sites_[2];  // the arena owner's, by network (0 generator, 1 discriminator)
+  std::vector<BNSite>& bn_sites(int net = 1) { return share_ ? share_->bn_sites(net) : bn_sites_[net]; }
+  // finds the site; the arena's owner creates it (mean 0, var 1, count 0)
+  Net::BNBuffers bn_site(const std::string& name, int C, int net = 1);
   PatchganNorm d_norm(int groups);
   // discriminate(): BatchNorm with batch statistics and a running update (nn.Module.train(), the default) or with the running
   // buffers (eval())
@@ -553,6 +566,9 @@ class Pipeline {
 // of the reference (models/warp_model.py:49-55, options/base_options.py:75-105); defaults 3 (rgb) / 19 (labels)
 Model* create_warp_model(Ctx& ctx, int B, int H, int W, bool is_train, float dropout, int body_channels = 3, int cloth_channels = 19,
                          Model* share = nullptr);
-Model* create_texture_model(Ctx& ctx, int B, int H, int W, bool is_train, int num_roi, int cloth_channels = 19, Model* share = nullptr);
+// netG: --netG of the texture stage (TextureNetG): 0 the ROI-pooled TextureModule, 1 unet_128; a sharing model takes its sharer's
+Model* create_texture_model(Ctx& ctx, int B, int H, int W, bool is_train, int num_roi, int cloth_channels = 19, Model* share = nullptr,
+                            int netG = NETG_SWAPNET);
+int texture_model_netG(const Model& m);       // TextureNetG of a texture model (throws for any other)
 
 }  // namespace swn

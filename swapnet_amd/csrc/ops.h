@@ -316,6 +316,13 @@ struct BatchNormArgs {
   // optional (training): the statistics' partial sums as the producing conv's epilogue left them (ConvFwdArgs::stat_partial)
   const double* partial_in = nullptr;
   int partial_chunks = 0;
+  // BatchNorm2d -> [act] -> Dropout(p) in the same apply pass (training mode only; eval applies no mask), NormActArgs' conventions:
+  // the factor is drop_scale(seed, element index, p), with seed = *seed_base * 0x9E3779B1 + salt when seed_base is given (captured
+  // step) -- what dropout_mask exports.  The amax slot of y is taken after the mask.  0 => today's kernels, untouched.
+  float drop_p = 0.f;
+  uint64_t seed = 0;
+  const uint64_t* seed_base = nullptr;
+  uint64_t salt = 0;
 };
 void batch_norm_fwd(Stream& s, const BatchNormArgs& a);
 struct BatchNormBwdArgs {
@@ -329,6 +336,12 @@ struct BatchNormBwdArgs {
   int groups = 1;
   int act = ACT_NONE;
   float* amax_out = nullptr;  // optional amax slot of dx
+  // the forward's dropout (BatchNormArgs): dy is multiplied by the same factor before anything else, so a dropped element adds 0
+  // to sum(dy'), sum(dy' xh), d gamma, d beta and dx
+  float drop_p = 0.f;
+  uint64_t seed = 0;
+  const uint64_t* seed_base = nullptr;
+  uint64_t salt = 0;
 };
 void batch_norm_bwd(Stream& s, const BatchNormBwdArgs& a);
 

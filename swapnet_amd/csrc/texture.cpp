@@ -91,6 +91,71 @@ void build_texture_generator(Net& n, const Var& tex, const float* rois_dev, int 
 }
 
 // ---------------------------------------------------------------------------------------
+// --netG unet_128 (models/texture_model.py define_G; modules/pix2pix_modules.py:113-262 under norm_layer = BatchNorm2d): the
+// plain pix2pix U-Net of Isola et al. 2017, UnetGenerator(3, 3, num_downs 7, ngf 64, BatchNorm2d, use_dropout), on the texture
+// image alone.  The same concatenation scheme as above with depth fixed at 7 (a 256 x 256 input leaves a 2 x 2 innermost map):
+//   e_1 = conv0(x)                               outermost down conv, no norm
+//   e_{d+1} = BN(conv_d(l_d))                    downnorm, d = 1 .. 5      [innermost d = 6: no norm]
+//   u_d = BN(convT_d(relu(C_{d+1})))  [+Dropout(0.5) for d = 4, 5]         upnorm, d = 6 .. 1
+//   out = tanh(convT_0(relu(C_1)))
+// use_bias is false under BatchNorm2d: no conv carries a bias except the outermost ConvTranspose2d, which keeps its default one.
+// Module indices inside a block: .model.1 down conv, .2 downnorm, .3 submodule, .5 up conv, .6 upnorm (innermost: .1, .3, .4).
+// ---------------------------------------------------------------------------------------
+static std::string unet128_prefix(int d) {
+  std::string p = "model";
+  for (int j = 0; j < d; ++j) p += j == 0 ? ".model.1" : ".model.3";
+  return p;
+}
+
+void build_unet128_generator(Net& n, const Var& tex, const Var& out,
+                             const std::function<Net::BNBuffers(const std::string& name, int C)>& site) {
+  const int B = tex.v.N, H = tex.v.H, W = tex.v.W;
+  const int depth = 7;
+  if (H != W || (H != 128 && H != 256))
+    throw Error(1, "UnetGenerator (--netG unet_128): crop_size must be 128 or 256 (7 stride-2 levels: innermost map 1 x 1 or 2 x 2), got " +
+                       std::to_string(W) + " x " + std::to_string(H));
+  if (!site) throw Error(1, "UnetGenerator (--netG unet_128): batch norm needs the running buffers' owner");
+  auto inner = [&](int d) { return d == 0 ? 64 : d == 1 ? 128 : d == 2 ? 256 : 512; };   // inner_nc of block d
+  std::vector<Var> C(depth), R(depth);      // C_d = [l_d | u_d], R_d = relu(C_d)
+  for (int d = 1; d < depth; ++d) {
+    const int ch = inner(d - 1), hw = H >> d;
+    C[d] = n.alloc_var(B, hw, hw, 2 * ch, true);
+    R[d] = n.alloc_var(B, hw, hw, 2 * ch, true);
+  }
+  // down path (the texture image is data: no input gradient)
+  n.conv(unet128_prefix(0) + ".model.0", tex, C[1].slice(0, 64), CK_K4S2, 3, 64, false, ACT_LRELU, nullptr, true);
+  Var innermost_mid;
+  for (int d = 1; d < depth; ++d) {
+    const int cin = inner(d - 1), cout = inner(d), hw = H >> (d + 1);
+    const std::string name = unet128_prefix(d) + ".model.1";
+    if (d < depth - 1) {
+      Var raw = n.alloc_var(B, hw, hw, cout, true);
+      n.conv(name, C[d].slice(0, cin), raw, CK_K4S2, cin, cout, false, ACT_NONE);
+      const std::string norm = unet128_prefix(d) + ".model.2";
+      n.batch_norm_act(norm, raw, C[d + 1].slice(0, cout), ACT_LRELU, 1, site(norm, cout));
+    } else {                                      // innermost: conv -> (uprelu) -> convT
+      innermost_mid = n.alloc_var(B, hw, hw, cout, true);
+      n.conv(name, C[d].slice(0, cin), innermost_mid, CK_K4S2, cin, cout, false, ACT_RELU);
+    }
+  }
+  // up path
+  for (int d = depth - 1; d >= 1; --d) {
+    const int ch = inner(d - 1), hw = H >> d;
+    const bool innermost = d == depth - 1;
+    Var raw = n.alloc_var(B, hw, hw, ch, true);
+    n.convT(unet128_prefix(d) + (innermost ? ".model.3" : ".model.5"), innermost ? innermost_mid : R[d + 1], raw, ch, false);
+    const std::string norm = unet128_prefix(d) + (innermost ? ".model.4" : ".model.6");
+    const float drop = (d >= 4 && d < depth - 1) ? 0.5f : 0.f;       // the num_downs - 5 = 2 ngf * 8 blocks built with use_dropout
+    n.batch_norm_act(norm, raw, C[d].slice(ch, ch), ACT_NONE, 1, site(norm, ch), drop);
+    n.act(C[d], R[d], ACT_RELU);
+  }
+  Var out_raw = n.alloc_var(B, H, W, 4, true);
+  n.convT(unet128_prefix(0) + ".model.3", R[1], out_raw, 3, true);
+  n.act(out_raw, out, ACT_TANH);
+  n.taps["fakes"] = out;
+}
+
+// ---------------------------------------------------------------------------------------
 // VGG16 features[0:30] split into the 5 slices of PerceptualLoss (perceptual.py:28-42).
 // Parameter names follow PerceptualLoss.state_dict(): net.<slice>.<vgg index>.{weight,bias}.
 // ---------------------------------------------------------------------------------------
@@ -142,8 +207,10 @@ class TextureModel final : public Model {
   }
 
   int Cc = 19, Ccp = 20, RC = 36;       // cloth channels (logical / padded), ROI-pooled texture channels 3 * num_roi
-  TextureModel(Ctx& c, int B_, int H_, int W_, bool train, int nroi, int cloth_channels, TextureModel* share = nullptr)
-      : Model(share), arenaV(share ? share->arenaV : ownV_) {
+  int netG = NETG_SWAPNET;              // --netG: the ROI-pooled TextureModule or the plain BatchNorm U-Net (unet_128)
+  TextureModel(Ctx& c, int B_, int H_, int W_, bool train, int nroi, int cloth_channels, TextureModel* share = nullptr,
+               int netG_ = NETG_SWAPNET)
+      : Model(share), arenaV(share ? share->arenaV : ownV_), netG(share ? share->netG : netG_) {
     ctx = &c; B = B_; H = H_; W = W_; is_train = train; num_roi = nroi;
     Cc = cloth_channels; Ccp = round_up(Cc, 4); RC = 3 * num_roi;
     if (Cc < 1 || Cc > 64) throw Error(1, "TextureModel: cloth_channels in [1,64]");
@@ -151,6 +218,9 @@ class TextureModel final : public Model {
     if (c.patchgan_norm != 0)
       throw Error(1, "TextureModel: a non-instance --norm is not implemented for the texture stage (its U-Net generator takes the same "
                      "norm layer and exists under InstanceNorm only)");
+    if (netG != NETG_SWAPNET && netG != NETG_UNET128) throw Error(1, "TextureModel: netG [" + std::to_string(netG) + "] is not recognized (0 swapnet, 1 unet_128)");
+    if (netG == NETG_UNET128 && !is_device_build())
+      throw Error(1, "TextureModel: --netG unet_128: BatchNorm is not implemented on the host simulator (HIP kernel only)");
     AllocScope mine(c, owned_allocs);
     G = std::make_unique<Net>(c, arenaG);
     G->keep_wino_inputs = train;
@@ -158,12 +228,14 @@ class TextureModel final : public Model {
     tex = G->alloc_var(B, H, W, 4, false);
     // first-layer buffers padded to multiples of 16 channels (zero pads meeting zero weight rows): 56 -> 64, 24 -> 32 and, for
     // VGG16's conv1_1, 4 -> 16 put those layers on the ring kernels (nets.cpp ring_pad; SWN_FIRST_RING=0: the round-3 layout)
-    unet_in = G->alloc_var(B, H, W, ring_pad(RC + Ccp), true);     // d(unet_in)[0:RC) feeds the encode branch
+    // (unet_128 has no cloth input: the cloths are staged for the discriminator's condition alone)
+    if (netG == NETG_SWAPNET) unet_in = G->alloc_var(B, H, W, ring_pad(RC + Ccp), true);     // d(unet_in)[0:RC) feeds the encode branch
     const int CdB = ring_pad(4 + Ccp);
     Dx = G->alloc_var(train ? 2 * B : B, H, W, CdB, train);
     rois = static_cast<float*>(c.alloc((size_t)B * num_roi * 4 * sizeof(float)));
     Var fake_slot = Dx.batch(0, B).slice(0, 4);
-    build_texture_generator(*G, tex, rois, num_roi, unet_in.slice(RC, Ccp), unet_in, fake_slot, H, Cc);
+    if (netG == NETG_SWAPNET) build_texture_generator(*G, tex, rois, num_roi, unet_in.slice(RC, Ccp), unet_in, fake_slot, H, Cc);
+    else build_unet128_generator(*G, tex, fake_slot, [this](const std::string& name, int C) { return bn_site(name, C, 0); });
     if (!arenaG.frozen) arenaG.allocate(c);
     G->finalize({fake_slot});
     losses = static_cast<float*>(c.alloc(L_COUNT * sizeof(float)));
@@ -275,7 +347,7 @@ class TextureModel final : public Model {
       nchw_to_nhwc(s, src, N, C, H, W, tex.v);
     } else if (slot == 2) {                            // cloths
       if (C != Cc) throw Error(1, "cloths must have " + std::to_string(Cc) + " channels");
-      nchw_to_nhwc(s, src, N, C, H, W, unet_in.v.slice(RC, Ccp));
+      if (unet_in.v.p) nchw_to_nhwc(s, src, N, C, H, W, unet_in.v.slice(RC, Ccp));
       nchw_to_nhwc(s, src, N, C, H, W, Dx.batch(0, B).v.slice(4, Ccp));
       if (is_train) nchw_to_nhwc(s, src, N, C, H, W, Dx.batch(B, B).v.slice(4, Ccp));
     } else if (slot == 3) {                            // target_textures
@@ -290,7 +362,7 @@ class TextureModel final : public Model {
     vt_done_ = false;
     if (N != B || Hh != H || Ww != W) throw Error(1, "set_input_labels: shape mismatch with the model's (B,H,W)");
     if (slot != 2) throw Error(1, "set_input_labels: slot has no label form");
-    labels_to_onehot(ctx->s, lab, unet_in.v.slice(RC, Ccp), Cc);
+    if (unet_in.v.p) labels_to_onehot(ctx->s, lab, unet_in.v.slice(RC, Ccp), Cc);
     labels_to_onehot(ctx->s, lab, Dx.batch(0, B).v.slice(4, Ccp), Cc);
     if (is_train) labels_to_onehot(ctx->s, lab, Dx.batch(B, B).v.slice(4, Ccp), Cc);
   }
@@ -305,12 +377,11 @@ class TextureModel final : public Model {
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std_[c]; }
     a.x_min = x_min; a.y_min = y_min; a.C = Cc;
     a.in_tex = tex.v;
-    a.cloth[0] = unet_in.v.slice(RC, Ccp);
-    a.cloth[1] = Dx.batch(0, B).v.slice(4, Ccp);
-    a.ncloth = 2;
+    a.ncloth = 0;
+    if (unet_in.v.p) a.cloth[a.ncloth++] = unet_in.v.slice(RC, Ccp);
+    a.cloth[a.ncloth++] = Dx.batch(0, B).v.slice(4, Ccp);
     if (is_train) {
-      a.cloth[2] = Dx.batch(B, B).v.slice(4, Ccp);
-      a.ncloth = 3;
+      a.cloth[a.ncloth++] = Dx.batch(B, B).v.slice(4, Ccp);
       a.tgt_tex = Dx.batch(B, B).v.slice(0, 4);
     }
     a.rois_out = rois;
@@ -324,6 +395,7 @@ class TextureModel final : public Model {
   int output_channels() const override { return 3; }
   void forward(bool training, uint64_t seed) override {        // texture_model.py:121-125
     G->training = training; G->seed = seed;
+    G->bn_training = training;         // (unet_128's BatchNorm sites: nn.Module.train() / eval(); the TextureModule has none)
     G->forward();
     vt_done_ = false;
   }
@@ -403,10 +475,15 @@ class TextureModel final : public Model {
   }
 };
 
-Model* create_texture_model(Ctx& ctx, int B, int H, int W, bool is_train, int num_roi, int cloth_channels, Model* share) {
+Model* create_texture_model(Ctx& ctx, int B, int H, int W, bool is_train, int num_roi, int cloth_channels, Model* share, int netG) {
   TextureModel* sh = dynamic_cast<TextureModel*>(share);
   if (share && !sh) throw Error(1, "shared model: the sharer is not a texture model");
-  return new TextureModel(ctx, B, H, W, is_train, num_roi, cloth_channels, sh);
+  return new TextureModel(ctx, B, H, W, is_train, num_roi, cloth_channels, sh, netG);
+}
+int texture_model_netG(const Model& m) {
+  const TextureModel* t = dynamic_cast<const TextureModel*>(&m);
+  if (!t) throw Error(1, "not a texture model");
+  return t->netG;
 }
 
 }  // namespace swn

@@ -16,6 +16,7 @@ NET_G, NET_D, NET_VGG = 0, 1, 2
 OPT_ADAMW, OPT_ADABOUND = 0, 1
 W_WEIGHT, W_GRAD, W_EXP_AVG, W_EXP_AVG_SQ = 0, 1, 2, 3
 NORM_KINDS = {"instance": 0, "batch": 1, "none": 2}       # --norm (swn_ctx_set_patchgan_norm)
+NETG_KINDS = {"swapnet": 0, "unet_128": 1}                # --netG of the texture stage (swn_texture_model_create_netG)
 
 
 class Context:
@@ -149,10 +150,16 @@ class NativeModel:
     NHWC arenas.  Tensors cross the boundary as NCHW fp32, exactly as the reference holds them."""
 
     def __init__(self, ctx, kind, batch, height, width, is_train=True, dropout=0.5, num_roi=12, body_channels=3,
-                 cloth_channels=19, n_layers_D=3, share=None, norm="instance"):
+                 cloth_channels=19, n_layers_D=3, share=None, norm="instance", netG="swapnet"):
         """share = another NativeModel of the same kind: the new model uses ITS parameter arenas (weights, gradients, Adam
         moments, step counters) and owns only activations -- the model of another batch size on the same training state
-        (swn_model_create_shared)."""
+        (swn_model_create_shared).  netG (texture models): "swapnet", the ROI-pooled TextureModule, or "unet_128", the plain
+        BatchNorm pix2pix U-Net on the textures alone; a sharing model inherits its sharer's."""
+        if netG not in NETG_KINDS:
+            raise ValueError("Cannot find implementation for " + str(netG))
+        if netG != "swapnet" and kind != "texture":
+            raise ValueError("netG %s belongs to the texture stage" % netG)
+        self.netG = netG
         self.ctx, self.lib, self.kind = ctx, ctx.lib, kind
         self.B, self.H, self.W, self.is_train = batch, height, width, is_train
         self.body_channels, self.cloth_channels = body_channels, cloth_channels
@@ -168,6 +175,7 @@ class NativeModel:
             self.lib.call("swn_model_create_shared", share.handle, batch, height, width, C.byref(h))
             self.is_train, self.body_channels, self.cloth_channels = share.is_train, share.body_channels, share.cloth_channels
             self.n_layers_D, self.out_channels, self.norm = share.n_layers_D, share.out_channels, share.norm
+            self.netG = share.netG
             self.handle = h
             self._keep = []
             return
@@ -181,8 +189,8 @@ class NativeModel:
                           C.c_float(dropout), body_channels, cloth_channels, C.byref(h))
             self.out_channels = cloth_channels
         elif kind == "texture":
-            self.lib.call("swn_texture_model_create_ex", ctx.handle, batch, height, width, int(is_train), num_roi,
-                          cloth_channels, C.byref(h))
+            self.lib.call("swn_texture_model_create_netG", ctx.handle, batch, height, width, int(is_train), num_roi,
+                          cloth_channels, NETG_KINDS[netG], C.byref(h))
             self.out_channels = 3
         else:
             raise ValueError("unknown model kind " + kind)
@@ -203,8 +211,8 @@ class NativeModel:
         return out
 
     def buffer_infos(self, net):
-        """state_dict() buffers of `net` (BatchNorm running statistics of the discriminator under norm="batch"):
-        name -> (shape, dtype)."""
+        """state_dict() buffers of `net` (BatchNorm running statistics: the discriminator under norm="batch", the generator of a
+        texture model with netG="unet_128"): name -> (shape, dtype)."""
         n = C.c_int()
         self.lib.call("swn_model_buffer_count", self.handle, net, C.byref(n))
         out = OrderedDict()
@@ -277,13 +285,23 @@ class NativeModel:
 
     def state_dict(self, net, which=W_WEIGHT, to_cpu=False):
         out = OrderedDict()
+        # a BatchNorm site's buffers follow its weight and bias, as in torch's module-tree order
+        by_site = OrderedDict()
+        if which == W_WEIGHT:
+            for k, info in self.buffer_infos(net).items():
+                by_site.setdefault(k.rsplit(".", 1)[0], []).append((k, info))
         for k, shape in self.param_infos(net).items():
             t = self.get_param(net, k, shape, which)
             out[k] = t.cpu() if to_cpu else t
-        if which == W_WEIGHT:
-            for k, (shape, dtype) in self.buffer_infos(net).items():
-                t = self.get_buffer(net, k, shape, dtype)
-                out[k] = t.cpu() if to_cpu else t
+            site = k.rsplit(".", 1)[0]
+            if k.endswith(".bias") and site in by_site:
+                for kb, (bshape, dtype) in by_site.pop(site):
+                    t = self.get_buffer(net, kb, bshape, dtype)
+                    out[kb] = t.cpu() if to_cpu else t
+        for entries in by_site.values():
+            for kb, (bshape, dtype) in entries:
+                t = self.get_buffer(net, kb, bshape, dtype)
+                out[kb] = t.cpu() if to_cpu else t
         self.ctx.sync()
         return out
 
@@ -844,3 +862,20 @@ class NativePipeline:
             self.close()
         except Exception:
             pass
+
+
+def op_batch_norm_act_dropout(ctx, x, weight, bias, dy=None, act=0, p=0.5, seed=0):
+    """BatchNorm2d -> [act] -> Dropout(p), training mode, forward (+ backward when dy is given) through
+    swn_op_batch_norm_act_dropout.  Returns (y, mask, dx, dweight, dbias): mask holds the factor (0 or 1/(1-p)) both passes
+    applied (None when p == 0)."""
+    xd = _dev(ctx, x)
+    dyd, wd, bd = _dev(ctx, dy), _dev(ctx, weight), _dev(ctx, bias)
+    n, c, h, w = xd.shape
+    y = torch.empty_like(xd)
+    mask = torch.empty_like(xd) if p > 0 else None
+    dx = None if dy is None else torch.empty_like(xd)
+    dw = torch.empty(c, dtype=torch.float32, device=ctx.device) if dy is not None else None
+    db = torch.empty_like(dw) if dw is not None else None
+    ctx.lib.call("swn_op_batch_norm_act_dropout", ctx.handle, _C.ptr(xd), _C.ptr(dyd), n, c, h, w, int(act), C.c_float(p),
+                 C.c_uint64(seed), _C.ptr(wd), _C.ptr(bd), _C.ptr(y), _C.ptr(mask), _C.ptr(dx), _C.ptr(dw), _C.ptr(db))
+    return y, mask, dx, dw, db

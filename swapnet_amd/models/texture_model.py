@@ -1,5 +1,5 @@
 """TextureModel of the reference (/root/reference/models/texture_model.py:16-180): texture stage
-= TextureModule generator against a PatchGAN conditioned on cat(cloth, texture); G loss = GAN +
+= TextureModule generator (--netG swapnet; or the plain pix2pix U-Net, --netG unet_128) against a PatchGAN conditioned on cat(cloth, texture); G loss = GAN +
 lambda_l1 * L1 + lambda_content * content + lambda_style * style."""
 from argparse import ArgumentParser
 
@@ -114,7 +114,11 @@ class TextureModel(BaseGAN):
                                  num_roi=self.opt.body_channels, img_size=self.opt.crop_size,
                                  norm_type=getattr(self.opt, "norm", "instance"), backend=self.backend)
         if netG == "unet_128":
-            raise NotImplementedError("netG unet_128 (plain pix2pix baseline) is not implemented natively")
+            # UnetGenerator(texture_channels, texture_channels, 7, 64, BatchNorm2d, use_dropout=True), called on the textures
+            # alone; rois and cloths are still staged by set_input (the cloths condition the discriminator)
+            from ..modules.pix2pix_modules import UnetGenerator
+            return UnetGenerator(self.opt.texture_channels, self.opt.texture_channels, 7, 64, norm_layer="batch",
+                                 use_dropout=True, backend=self.backend)
         raise ValueError("Cannot find implementation for " + netG)
 
     # self.textures / self.cloths / self.targets: plain attributes on the float hand-over; after a compact batch they are

@@ -30,11 +30,15 @@ def _construction_order(layers):
     (= state-dict order); the pix2pix U-Net is built recursively from the innermost block outwards, down
     conv before up conv in each block (modules/pix2pix_modules.py:113-177,208-246), while its state dict
     (module tree) lists the outermost block first."""
-    unet = [n for n in layers if n.startswith("unet.")]
+    # the TextureModule holds the U-Net as `unet`; a bare UnetGenerator (--netG unet_128) has the prefix `model` itself
+    lead = "unet." if any(n.startswith("unet.") for n in layers) else ""
+    is_unet = lambda n: n.startswith(lead + "model.model.")
+    unet = [n for n in layers if is_unet(n)]
     if not unet:
         return list(layers)
-    rest = [n for n in layers if not n.startswith("unet.")]           # `encode` is defined before the U-Net
-    depth = lambda n: (len(n.split(".")) - 4) // 2                    # unet.model.model.K = block 0
+    rest = [n for n in layers if not is_unet(n)]                      # `encode` is defined before the U-Net
+    depth = lambda n: (len(n[len(lead):].split(".")) - 3) // 2        # [unet.]model.model.K = block 0
+    # (a block's BatchNorm layers sit between its convs here; they draw nothing at construction and the caller skips them)
     order = sorted(unet, key=lambda n: (-depth(n), int(n.rsplit(".", 1)[1])))
     return rest + order
 
@@ -82,7 +86,9 @@ class Identity(torch.nn.Module):
 def get_norm_layer(norm_type="instance"):
     """modules.get_norm_layer (modules/__init__.py:53-74).  The native networks take the layer by name: instance (the reference's
     default, base_gan.py:72-77), batch (BatchNorm2d, affine, running statistics) or none.  The discriminators implement all
-    three (modules/discriminators.py); the generators instance only."""
+    three (modules/discriminators.py).  Every generator exists under one layer: WarpModule and TextureModule under instance,
+    the texture stage's plain U-Net (--netG unet_128, modules/pix2pix_modules.UnetGenerator) under batch -- as the reference
+    hard-codes it -- so --norm does not select a generator's layer."""
     if norm_type in ("instance", "batch", "none"):
         return norm_type
     raise NotImplementedError("normalization layer [%s] is not found" % norm_type)

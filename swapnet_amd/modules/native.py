@@ -17,12 +17,13 @@ class NativeBackend:
     counters are simply the same memory -- nothing is copied when the batch size changes back and forth."""
 
     def __init__(self, kind, is_train=True, dropout=0.5, num_roi=12, ctx=None, lib=None, device=None,
-                 default_shape=(1, 64, 64), body_channels=3, cloth_channels=19):
+                 default_shape=(1, 64, 64), body_channels=3, cloth_channels=19, netG="swapnet"):
         self.kind, self.is_train, self.dropout, self.num_roi = kind, is_train, dropout, num_roi
         self.body_channels, self.cloth_channels = body_channels, cloth_channels
         self.default_shape = tuple(default_shape)
         self.n_layers_D = 3         # define_D(..., n_layers_D): set by NLayerDiscriminator before the first model exists
         self.norm = "instance"      # define_D(..., norm): the discriminator's norm layer, set the same way
+        self.netG = netG            # texture stage: --netG (define_G sets it before the first model exists)
         self.ctx = ctx or engine.default_context(device=device, lib=lib)
         self.models = {}
         self.cur = None
@@ -39,7 +40,8 @@ class NativeBackend:
             root = next(iter(self.models.values()), None)          # the first model owns the arenas, every later one shares them
             m = engine.NativeModel(self.ctx, self.kind, key[0], key[1], key[2], is_train=self.is_train,
                                    dropout=self.dropout, num_roi=self.num_roi, body_channels=self.body_channels,
-                                   cloth_channels=self.cloth_channels, n_layers_D=self.n_layers_D, share=root, norm=self.norm)
+                                   cloth_channels=self.cloth_channels, n_layers_D=self.n_layers_D, share=root, norm=self.norm,
+                                   netG=self.netG)
             m.set_hyper(**self.hyper)
             for net, kw in self.optim.items():
                 m.set_optimizer(net, **kw)
