@@ -66,8 +66,10 @@ int swn_ctx_set_overlap(swn_ctx* ctx, int on);
  * PixelDiscriminator (swn_model_set_hyper fails). */
 int swn_ctx_set_patchgan_layers(swn_ctx* ctx, int n_layers);
 /* discriminators.define_D(..., norm) -> get_norm_layer(norm) (modules/discriminators.py:77, modules/__init__.py:53-74;
- * models/base_gan.py:72-77,147-149): the norm layer of the discriminator of every WARP model created on this context
- * AFTERWARDS.  0 = instance (default), 1 = batch (nn.BatchNorm2d, affine, running statistics), 2 = none (identity).
+ * models/base_gan.py:72-77,147-149): --norm for every model created on this context AFTERWARDS -- the norm layer of the warp
+ * stage's discriminator, of the texture stage's discriminator, and of the TextureModule's pix2pix U-Net
+ * (modules/swapnet_modules.py:176-187; its `encode` branch keeps InstanceNorm, and the warp generator hard-codes it).
+ * 0 = instance (default), 1 = batch (nn.BatchNorm2d, affine, running statistics), 2 = none (identity).
  * Under 1 and 2 the convs in front of a norm layer carry no bias (use_bias is true only under InstanceNorm2d,
  * modules/discriminators.py:104-107,151-154): the state dict has no model.{2,5,8}.bias / net.2.bias.  Under 1 every norm site
  * adds model.K.weight / model.K.bias (K = 3, 6, ...; net.3 for the PixelDiscriminator) to the discriminator's parameters -- the
@@ -76,11 +78,16 @@ int swn_ctx_set_patchgan_layers(swn_ctx* ctx, int n_layers);
  * times, as the reference's three discriminator calls do (models/warp_model.py:115-121,157-158): fake batch, real batch -- the
  * two halves of the one 2B pass, normalised separately -- then the fakes through the updated discriminator.  Under data
  * parallelism the statistics stay local to each rank (torch DDP's default).
- * Not implemented (the library's "not implemented" error): texture models under kind != 0 (the flag also selects the norm layer
- * of the texture stage's U-Net generator, modules/swapnet_modules.py:176-187, which exists under InstanceNorm only); the
- * gradient-penalty modes under kind != 0; kind 1 on the CI simulator (HIP kernels only).
- * The flag does not reach the generator (net 0): the only generator with BatchNorm sites is the texture stage's unet_128
- * (swn_texture_model_create_netG), which has them under kind 0 -- and, as a texture model, refuses any other kind. */
+ * The TextureModule's U-Net under 1 and 2: no conv carries a bias but the outermost ConvTranspose2d; under 1 every down-norm
+ * (<block>.model.2) and up-norm (<block>.model.6, innermost .model.4) is a BatchNorm site of net 0 with weight, bias and running
+ * buffers, the upnorm -> Dropout sites fused as in unet_128; an inference model (and swn_pipeline's second stage) normalises with
+ * the running buffers.  The unet_128 generator (swn_texture_model_create_netG) ignores the flag -- BatchNorm2d whatever it
+ * says -- and its discriminator follows it.
+ * A gradient-penalty step (warp stage) under kind 1 updates the running statistics four times: fake, real, the interpolate x_hat
+ * (the reference calls the module in train mode, modules/loss.py:157-162), then the generator pass's fakes; the second-order pass
+ * walks BatchNorm with swn_op_batch_norm_act_bwd2's kernels and, under kind 2, conv -> LeakyReLU alone.
+ * Device library only: on the CI simulator (no BatchNorm kernels) kind 1, texture models under kind != 0 and the gradient-penalty
+ * modes under kind != 0 answer with the library's "not implemented" error.  Synchronised statistics across ranks: not implemented. */
 int swn_ctx_set_patchgan_norm(swn_ctx* ctx, int kind);
 int swn_ctx_sync(swn_ctx* ctx);
 int swn_ctx_bytes_allocated(swn_ctx* ctx, size_t* out);
@@ -510,6 +517,11 @@ int swn_op_norm_act_dropout(swn_ctx* ctx, const float* x, const float* dy, int n
  * backward, returns uy = d<gx,u>/d gy and ax = d<gx,u>/d x.  NCHW fp32, C % 4 == 0. */
 int swn_op_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const float* u, int n, int c, int h, int w, int act,
                          float* uy, float* ax);
+/* the same step through y = act(BatchNorm2d(x)) in training mode (biased statistics over N*H*W, eps 1e-5, affine gamma / beta of c
+ * device floats): uy = d<gx,u>/d gy, ax = d<gx,u>/d x and dgamma = d<gx,u>/d gamma (c device floats; d<gx,u>/d beta is 0 for the
+ * piecewise-linear activations).  NCHW fp32, C % 4 == 0.  Device library only: the CI simulator answers "not implemented". */
+int swn_op_batch_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const float* u, const float* gamma, const float* beta,
+                               int n, int c, int h, int w, int act, float* uy, float* ax, float* dgamma);
 /* The kernels between the convolutions, each launcher of ops.h called alone on channel-slice views (tests).  Convention of the three
  * entry points below: tensors are NCHW device floats; every operand lives in an NHWC buffer of lead + c + pad channels (lead, pad
  * multiples of 4, given per operand in `lead_pad` = {lead, pad} pairs), every byte of which holds 0x7f before the logical channels

@@ -126,6 +126,7 @@ _PROTOS = {
     "swn_op_elementwise": ([_vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_i), _fp, _fp, _fp], _i),
     "swn_op_resample": ([_vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), _fp, _fp, _vp, _fp], _i),
     "swn_op_norm_act_bwd2": ([_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp], _i),
+    "swn_op_batch_norm_act_bwd2": ([_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp], _i),
     "swn_op_norm_act_dropout": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, C.c_uint64, _fp, _fp, _fp], _i),
     "swn_op_adamw": ([_vp, _fp, _fp, _fp, _fp, C.c_size_t, _f, _f, _f, _f, _f, _i], _i),
     "swn_op_adabound": ([_vp, _fp, _fp, _fp, _fp, C.c_size_t, _f, _f, _f, _f, _f, _f, _f, _f, _i], _i),

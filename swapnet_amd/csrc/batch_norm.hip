@@ -6,6 +6,7 @@
 // No floating-point atomics: two runs on the same inputs are bit-identical.
 // Optionally Dropout(p) follows in the same apply pass, forward and backward (the upnorm -> Dropout sites of the pix2pix U-Net,
 // Isola et al. 2017): separate instantiations, so a call without dropout launches the kernels it always did.
+// batch_norm_bwd2: the second-order (reverse over reverse) step of the gradient penalties through act(BN(x)), one group, same split.
 // Reference: modules/__init__.py:62-65 (BatchNorm2d(affine=True, track_running_stats=True)), modules/discriminators.py:113-128,160-162.
 #include <algorithm>
 
@@ -234,6 +235,142 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(typename BNArg<DROP>:
   amax_fold(am, p.amax_out);
 }
 
+// ---- second-order step through act(BN(x)) -- ops.h batch_norm_bwd2 ---------------------------------------------------
+// One group.  New kernels with an argument block of their own: the first-order kernels above and BNp stay as they are.
+struct BN2p {
+  const float *u, *gy, *x; int ucs, gycs, xcs;
+  float *uy, *ax; int uycs, axcs;
+  const float *stats, *fold, *gamma;
+  double* partial;      // [N][nchunk][C][5]: sums of u, u xh, gm, gm xh, u gm
+  double* coef;         // [C][5] = <u>, <u xh>, <gm>, <gm xh>, <u gm> - <u><gm> - <u xh><gm xh>
+  float* dgamma;
+  int N, HW, C, nchunk, chunk, act;
+};
+
+// the five sums over a pixel chunk of one image; gm = act'(z) * gy with z = x * scale + shift, the forward's own value
+__global__ __launch_bounds__(256) void bn2_partial_kernel(BN2p p) {
+  __shared__ double red[256 * 10];      // two halves of 256 x 5: the 20 sums of a thread's 4 channels go through in two rounds
+  const int C4 = p.C >> 2;
+  const int rows = 256 / C4;
+  const int t = threadIdx.x, tx = t % C4, ty = t / C4;
+  const int n = blockIdx.y, ch = blockIdx.x;
+  const int c0 = ch * p.chunk, c1 = min(p.HW, c0 + p.chunk);
+  double s[4][5];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < 5; ++k) s[j][k] = 0;
+  if (ty < rows) {
+    float mean[4], rstd[4], sc[4], sh[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = tx * 4 + j;
+      mean[j] = p.stats[c * 2]; rstd[j] = p.stats[c * 2 + 1];
+      sc[j] = p.fold[c]; sh[j] = p.fold[p.C + c];
+    }
+    for (int pix = c0 + ty; pix < c1; pix += rows) {
+      const size_t e = (size_t)n * p.HW + pix;
+      const float4 xv = *reinterpret_cast<const float4*>(p.x + e * p.xcs + tx * 4);
+      const float4 gv = *reinterpret_cast<const float4*>(p.gy + e * p.gycs + tx * 4);
+      const float4 uv = *reinterpret_cast<const float4*>(p.u + e * p.ucs + tx * 4);
+      const float xa[4] = {xv.x, xv.y, xv.z, xv.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w}, ua[4] = {uv.x, uv.y, uv.z, uv.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double xh = ((double)xa[j] - (double)mean[j]) * (double)rstd[j];
+        const double uu = ua[j];
+        const double gm = (double)(ga[j] * bn_act_grad(xa[j] * sc[j] + sh[j], p.act));
+        s[j][0] += uu; s[j][1] += uu * xh; s[j][2] += gm; s[j][3] += gm * xh; s[j][4] += uu * gm;
+      }
+    }
+  }
+  // two channels per round: red[t * 10 + (j & 1) * 5 + k]
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int k = 0; k < 5; ++k) red[t * 10 + j * 5 + k] = s[h * 2 + j][k];
+    __syncthreads();
+    if (ty == 0) {
+      for (int r = 1; r < rows; ++r)
+#pragma unroll
+        for (int k = 0; k < 10; ++k) red[t * 10 + k] += red[(r * C4 + tx) * 10 + k];
+      double* o = p.partial + (((size_t)n * p.nchunk + ch) * p.C + tx * 4 + h * 2) * 5;
+#pragma unroll
+      for (int k = 0; k < 10; ++k) o[k] = red[t * 10 + k];
+    }
+    __syncthreads();
+  }
+}
+
+// 16 channels x 16 lanes per block, the reduction order of bn_finalize_kernel: each lane sums every 16th (image, chunk) partial,
+// lane 0 the 16 lanes.  Writes the means the apply pass needs and the second-order gradient of gamma,
+//   d gamma = sum v gm = rstd M (<u gm> - <u><gm> - <u xh><gm xh>).
+__global__ __launch_bounds__(256) void bn2_finalize_kernel(BN2p p) {
+  __shared__ double red[256 * 5];
+  const int cl = threadIdx.x & 15, ln = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl;
+  const int cnt = p.N * p.nchunk;
+  const double M = (double)p.N * p.HW;
+  double a[5] = {0, 0, 0, 0, 0};
+  if (c < p.C)
+    for (int i = ln; i < cnt; i += 16) {
+      const double* o = p.partial + ((size_t)i * p.C + c) * 5;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) a[k] += o[k];
+    }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) red[threadIdx.x * 5 + k] = a[k];
+  __syncthreads();
+  if (ln == 0 && c < p.C) {
+    double S[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+#pragma unroll
+      for (int k = 0; k < 5; ++k) S[k] += red[(j * 16 + cl) * 5 + k];
+    const double mu = S[0] / M, muh = S[1] / M, mg = S[2] / M, mgh = S[3] / M;
+    const double K = S[4] / M - mu * mg - muh * mgh;
+    double* o = p.coef + (size_t)c * 5;
+    o[0] = mu; o[1] = muh; o[2] = mg; o[3] = mgh; o[4] = K;
+    if (p.dgamma) p.dgamma[c] = (float)((double)p.stats[c * 2 + 1] * M * K);
+  }
+}
+
+// uy = act'(z) gamma rstd (u - <u> - xh <u xh>)
+// ax = -rstd^2 gamma [ xh K + <gm xh> (u - <u> - xh <u xh>) + <u xh> (gm - <gm> - xh <gm xh>) ]      (q = gamma gm factored out)
+__global__ __launch_bounds__(256) void bn2_apply_kernel(BN2p p) {
+  const int C4 = p.C >> 2;
+  const size_t total = (size_t)p.N * p.HW * C4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = i / C4;
+    const int c = (int)(i - e * C4) * 4;
+    const float4 xv = *reinterpret_cast<const float4*>(p.x + e * p.xcs + c);
+    const float4 gv = *reinterpret_cast<const float4*>(p.gy + e * p.gycs + c);
+    const float4 uv = *reinterpret_cast<const float4*>(p.u + e * p.ucs + c);
+    const float4 sc = *reinterpret_cast<const float4*>(p.fold + c);
+    const float4 sh = *reinterpret_cast<const float4*>(p.fold + p.C + c);
+    const float4 gmv = *reinterpret_cast<const float4*>(p.gamma + c);
+    const float xa[4] = {xv.x, xv.y, xv.z, xv.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w}, ua[4] = {uv.x, uv.y, uv.z, uv.w};
+    const float sca[4] = {sc.x, sc.y, sc.z, sc.w}, sha[4] = {sh.x, sh.y, sh.z, sh.w}, gma[4] = {gmv.x, gmv.y, gmv.z, gmv.w};
+    float oy[4], ox[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float mean = p.stats[(c + j) * 2];
+      const double rstd = p.stats[(c + j) * 2 + 1], gamma = gma[j];
+      const double* m = p.coef + (size_t)(c + j) * 5;
+      const double mu = m[0], muh = m[1], mg = m[2], mgh = m[3], K = m[4];
+      const float ad = bn_act_grad(xa[j] * sca[j] + sha[j], p.act);
+      const double xh = ((double)xa[j] - (double)mean) * rstd;
+      const double gm = (double)(ga[j] * ad);
+      const double ju = (double)ua[j] - mu - xh * muh;
+      oy[j] = (float)((double)ad * gamma * rstd * ju);
+      ox[j] = (float)(-rstd * rstd * gamma * (xh * K + mgh * ju + muh * (gm - mg - xh * mgh)));
+    }
+    *reinterpret_cast<float4*>(p.uy + e * p.uycs + c) = make_float4(oy[0], oy[1], oy[2], oy[3]);
+    *reinterpret_cast<float4*>(p.ax + e * p.axcs + c) = make_float4(ox[0], ox[1], ox[2], ox[3]);
+  }
+}
+
 inline unsigned bn_grid(size_t total) {
   const size_t b = (total + 255) / 256;
   return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), 256 * 16);
@@ -343,6 +480,31 @@ void batch_norm_bwd(Stream& s, const BatchNormBwdArgs& a) {
   if (drop) hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, agrid, dim3(256), 0, hs(s), pd);
   else hipLaunchKernelGGL(bn_bwd_apply_kernel<0>, agrid, dim3(256), 0, hs(s), p);
   check_launch("batch_norm_bwd");
+}
+
+void batch_norm_bwd2(Stream& s, const BatchNormBwd2Args& a) {
+  const BNp c = bn_common(a.x, 1, "batch_norm_bwd2 x");
+  bn_check_view(a.u, "batch_norm_bwd2 u"); bn_check_view(a.gy, "batch_norm_bwd2 gy");
+  bn_check_view(a.uy, "batch_norm_bwd2 uy"); bn_check_view(a.ax, "batch_norm_bwd2 ax");
+  if (!a.stats || !a.fold || !a.gamma) throw Error(1, "batch_norm_bwd2: gamma and the forward's stats and fold buffers are required");
+  if (((uintptr_t)a.fold & 15) || ((uintptr_t)a.gamma & 15)) throw Error(1, "batch_norm_bwd2: fold and gamma must be 16-byte aligned");
+  for (const TView* v : {&a.u, &a.gy, &a.uy, &a.ax})
+    if (v->N != a.x.N || v->H != a.x.H || v->W != a.x.W || v->C != a.x.C) throw Error(1, "batch_norm_bwd2: shape mismatch");
+  BN2p p{};
+  p.u = a.u.p; p.ucs = a.u.cs; p.gy = a.gy.p; p.gycs = a.gy.cs; p.x = a.x.p; p.xcs = a.x.cs;
+  p.uy = a.uy.p; p.uycs = a.uy.cs; p.ax = a.ax.p; p.axcs = a.ax.cs;
+  p.stats = a.stats; p.fold = a.fold; p.gamma = a.gamma; p.dgamma = a.dgamma;
+  p.N = c.N; p.HW = c.HW; p.C = c.C; p.act = a.act;
+  batch_norm_plan_chunks(p.HW, p.N, p.C, p.nchunk, p.chunk);
+  p.partial = reinterpret_cast<double*>(s.ws);
+  const size_t pbytes = ((size_t)p.N * p.nchunk * p.C * 5 * 8 + 255) / 256 * 256;
+  p.coef = reinterpret_cast<double*>(s.ws + pbytes);
+  if (pbytes + (size_t)p.C * 5 * 8 > s.ws_bytes) throw Error(1, "batch_norm_bwd2: workspace too small");
+  if (route_on()) route_note("batch_norm_bwd2[bn2_partial_kernel, bn2_finalize_kernel, bn2_apply_kernel]");
+  hipLaunchKernelGGL(bn2_partial_kernel, dim3(p.nchunk, p.N), dim3(256), 0, hs(s), p);
+  hipLaunchKernelGGL(bn2_finalize_kernel, dim3(ceil_div(p.C, 16)), dim3(256), 0, hs(s), p);
+  hipLaunchKernelGGL(bn2_apply_kernel, dim3(bn_grid((size_t)p.N * p.HW * (p.C / 4))), dim3(256), 0, hs(s), p);
+  check_launch("batch_norm_bwd2");
 }
 
 }  // namespace swn

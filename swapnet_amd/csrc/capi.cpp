@@ -228,7 +228,8 @@ int swn_model_set_hyper(swn_model* m, const swn_hyper* h) {
     REQUIRE(h->gp_mode >= 0 && h->gp_mode <= 3, "gradient penalty mode not implemented");
     REQUIRE(h->gp_mode == 0 || m->m->supports_gradient_penalty(),
             "gradient penalty modes are not implemented for the texture model (the reference's call fails there too), for the "
-            "1x1 PixelDiscriminator, nor for a discriminator under --norm batch / none (the second-order pass walks InstanceNorm)");
+            "1x1 PixelDiscriminator, nor -- on the host simulator -- for a discriminator under --norm batch / none (the second-order "
+            "pass through BatchNorm and without a norm layer is in the device library only)");
     y.gp_mode = h->gp_mode; y.lambda_gp = h->lambda_gp;
   });
 }
@@ -1209,6 +1210,35 @@ int swn_op_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const fl
     norm_act_bwd2(tmp.s, b2);
     nhwc_to_nchw(tmp.s, uv.g, uy, c);
     nhwc_to_nchw(tmp.s, xv.g, ax, c);
+    stream_sync(tmp.s);
+  });
+}
+// the BatchNorm counterpart: training-mode forward (one group, no running buffers) for stats and fold, then ops.h batch_norm_bwd2
+int swn_op_batch_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const float* u, const float* gamma, const float* beta,
+                               int n, int c, int h, int w, int act, float* uy, float* ax, float* dgamma) {
+  return guard([&] {
+    REQUIRE(ctx && x && gy && u && gamma && beta && uy && ax && dgamma && c % 4 == 0, "bad argument (C must be a multiple of 4)");
+    REQUIRE(n > 0 && c > 0 && h > 0 && w > 0, "bad shape");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    Var xv = net.alloc_var(n, h, w, c, true), yv = net.alloc_var(n, h, w, c, true), uv = net.alloc_var(n, h, w, c, true);
+    float* par = static_cast<float*>(tmp.alloc((size_t)7 * c * sizeof(float)));      // gamma, beta, stats [C][2], fold [2][C], d gamma
+    float *gd = par, *bd = par + c, *stats = par + 2 * c, *fold = par + 4 * c, *dg = par + 6 * c;
+    dev_copy(tmp.s, gd, gamma, c * sizeof(float));
+    dev_copy(tmp.s, bd, beta, c * sizeof(float));
+    nchw_to_nhwc(tmp.s, x, n, c, h, w, xv.v);
+    nchw_to_nhwc(tmp.s, gy, n, c, h, w, yv.g);
+    nchw_to_nhwc(tmp.s, u, n, c, h, w, uv.v);
+    BatchNormArgs f;
+    f.x = xv.v; f.y = yv.v; f.gamma = gd; f.beta = bd; f.stats = stats; f.fold = fold; f.act = act;
+    batch_norm_fwd(tmp.s, f);
+    BatchNormBwd2Args b2;
+    b2.u = uv.v; b2.gy = yv.g; b2.x = xv.v; b2.stats = stats; b2.fold = fold; b2.gamma = gd;
+    b2.uy = uv.g; b2.ax = xv.g; b2.dgamma = dg; b2.act = act;
+    batch_norm_bwd2(tmp.s, b2);
+    nhwc_to_nchw(tmp.s, uv.g, uy, c);
+    nhwc_to_nchw(tmp.s, xv.g, ax, c);
+    dev_copy(tmp.s, dgamma, dg, c * sizeof(float));
     stream_sync(tmp.s);
   });
 }

@@ -1551,7 +1551,7 @@ void Model::discriminate(const float* x_nchw, float* pred_nchw) {
 void Model::set_gp_random(const float* alpha_dev, const float* beta_nchw_dev) {
   if (!is_train || d_cimap_.empty()) throw Error(1, "set_gp_random: the model has no discriminator");
   if (!gp_) {
-    AllocScope mine(*ctx, owned_allocs); gp_ = std::make_unique<GradPenalty>(*ctx, arenaD, B, H, W, d_layers_);
+    AllocScope mine(*ctx, owned_allocs); gp_ = std::make_unique<GradPenalty>(*ctx, arenaD, B, H, W, d_layers_, d_norm(1));
   }
   if (alpha_dev) { dev_copy(ctx->s, gp_->alpha_buffer(), alpha_dev, (size_t)B * sizeof(float)); gp_alpha_set_ = true; }
   if (beta_nchw_dev) {                       // reference channel order (B, 22, H, W) -> buffer order, pads stay 0
@@ -1575,7 +1575,7 @@ void Model::set_gp_random(const float* alpha_dev, const float* beta_nchw_dev) {
 }
 void Model::run_gradient_penalty(const TView& real, const TView& fake) {
   if (!gp_) {
-    AllocScope mine(*ctx, owned_allocs); gp_ = std::make_unique<GradPenalty>(*ctx, arenaD, B, H, W, d_layers_);
+    AllocScope mine(*ctx, owned_allocs); gp_ = std::make_unique<GradPenalty>(*ctx, arenaD, B, H, W, d_layers_, d_norm(1));
   }
   const TView beta = gp_->beta_buffer();
   // library RNG: a function of the step seed the caller handed to forward() (torch.initial_seed(), the step counter and --
@@ -1742,6 +1742,9 @@ __attribute__((weak)) void batch_norm_fwd(Stream&, const BatchNormArgs&) {
 }
 __attribute__((weak)) void batch_norm_bwd(Stream&, const BatchNormBwdArgs&) {
   throw Error(1, "batch_norm_bwd: BatchNorm is not implemented on the host simulator (HIP kernel only)");
+}
+__attribute__((weak)) void batch_norm_bwd2(Stream&, const BatchNormBwd2Args&) {
+  throw Error(1, "batch_norm_bwd2: BatchNorm is not implemented on the host simulator (HIP kernel only)");
 }
 __attribute__((weak)) void time_launches(Stream&, int, int, const std::function<void()>&, float*) {
   throw Error(1, "time_launches: device timing is not implemented on the host simulator");

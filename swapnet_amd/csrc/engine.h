@@ -62,11 +62,10 @@ struct Ctx {
   // every model created on this context afterwards (3 = the reference's "basic" 70x70 PatchGAN)
   int patchgan_layers = 3;
   // discriminators.define_D(..., norm) (modules/discriminators.py:77, modules/__init__.py:53-74; base_gan.py:147): the norm layer of the
-  // discriminator of every WARP model created on this context afterwards -- 0 instance (the reference's default), 1 batch
-  // (BatchNorm2d, affine, running statistics: Net::batch_norm_act), 2 none (identity).  Under 1 and 2 the inner convs have no bias
-  // (use_bias is true only under InstanceNorm2d, :104-107,151-154).  The texture stage's generator takes the same flag in the
-  // reference; its generators exist under one norm layer each (TextureModule: instance; --netG unet_128: batch, whatever this says),
-  // so texture models refuse a non-instance kind.
+  // discriminator of every model created on this context afterwards, and of the TextureModule's pix2pix U-Net -- 0 instance (the
+  // reference's default), 1 batch (BatchNorm2d, affine, running statistics: Net::batch_norm_act), 2 none (identity).  Under 1 and 2
+  // the inner convs have no bias (use_bias is true only under InstanceNorm2d, :104-107,151-154).  --netG unet_128 is BatchNorm
+  // whatever this says.  1, and the texture stage under 1 or 2, in the device library only.
   int patchgan_norm = 0;
   explicit Ctx(void* stream, size_t ws_bytes);
   explicit Ctx(const Stream& shared);      // borrows stream + workspace of another context
@@ -321,8 +320,11 @@ struct PatchganNorm {
 };
 Var build_patchgan(Net& net, const Var& x, int n_layers, const std::vector<int32_t>& cimap, int in_grad_channels = 0,
                    const PatchganNorm& norm = PatchganNorm());
+// norm_kind: the U-Net's norm layer (Ctx::patchgan_norm: 0 instance, 1 batch with the running buffers from site(name, C), 2 none);
+// the encode branch keeps its InstanceNorm
 void build_texture_generator(Net& net, const Var& tex, const float* rois_dev, int num_roi, const Var& cloth_cat,
-                             const Var& unet_in, const Var& out, int img_size, int cloth_channels = 19);
+                             const Var& unet_in, const Var& out, int img_size, int cloth_channels = 19, int norm_kind = 0,
+                             const std::function<Net::BNBuffers(const std::string& name, int C)>& site = nullptr);
 // --netG unet_128: the plain pix2pix U-Net (Isola et al. 2017) under BatchNorm2d, UnetGenerator(3, 3, num_downs 7, ngf 64,
 // use_dropout) on the 3-channel texture buffer -- no ROIs, no cloth input.  site(name, C): the running buffers of a norm site
 // (the model: nets bound to one arena share them).  H = W in {128, 256}.
@@ -340,7 +342,9 @@ bool first_ring_on();
 // ---- gradient penalty (gp.cpp): second-order pass through PatchGAN for --gan_mode wgan-gp / dragan-gp / dragan-lp ----
 class GradPenalty {
  public:
-  GradPenalty(Ctx& c, ParamArena& arenaD, int B, int H, int W, int n_layers = 3);
+  // norm: the discriminator's norm layer (kind 1: gamma / beta in arenaD, the running buffers from norm.site; groups is not used:
+  // the penalty's pass is one B batch)
+  GradPenalty(Ctx& c, ParamArena& arenaD, int B, int H, int W, int n_layers = 3, const PatchganNorm& norm = PatchganNorm());
   ~GradPenalty();
   // real / fake: the conditioned (B, H, W, 24) halves of the discriminator's input buffer.  gp_mode 1 wgan-gp,
   // 2 dragan-gp, 3 dragan-lp.  Adds grad_scale * lambda_gp * d gp / d theta to the discriminator's gradient arena and
@@ -355,8 +359,12 @@ class GradPenalty {
     size_t woff = 0, boff = (size_t)-1;
     int kind = 0;                  // 0: k4 s2 p1, 1: k4 s1 p1
     int Cin = 0, Co = 0, Cop = 0;  // input buffer channels, logical / padded output channels
-    bool norm = false;
+    bool norm = false;             // a norm layer follows the conv (none under kind 2)
+    bool bias = true;              // the conv carries a bias (under kinds 1 and 2 only the first and the prediction conv do)
     float* stats = nullptr;
+    size_t goff = 0, beoff = 0;    // kind 1: gamma / beta of the BatchNorm site in the arena
+    float* fold = nullptr;
+    Net::BNBuffers run;
     float* dg = nullptr;           // input-gradient operand (repack_dgrad), refreshed every run
     Var raw, h;                    // conv output (l = 1..n_layers) and activation; .g = first-backward gradients
     TView u_raw, u_h, a_raw, a_h, tmp, gr0;
@@ -364,10 +372,12 @@ class GradPenalty {
   void conv(int l, const TView& x, const TView& y, bool bias, int act);
   void dgrad(int l, const TView& dy, const TView& dx);
   void wgrad(int l, const TView& x, const TView& dy, float* arena);
+  void bn_bwd(int l, const TView& dy, const TView& dx, float* arena);
   Ctx& ctx_;
   ParamArena& A_;
   int B_;
   int nl_ = 3, NL_ = 5;                // stride-2 levels of the PatchGAN; its convs (n_layers + 2)
+  int kind_ = 0;                       // the norm layer: 0 instance, 1 batch, 2 none
   int Cd_ = 24, Cd_logical_ = 22;      // D input buffer channels / the reference's channel count
  
   std::unique_ptr<Net> net_;

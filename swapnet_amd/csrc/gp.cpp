@@ -14,6 +14,11 @@
 // LeakyReLU is piecewise linear (mask only); InstanceNorm is the one non-linear layer: ops.h norm_act_bwd2 gives
 // both J u and the injected adjoint.  Every contraction reuses the MFMA conv / wgrad kernels of the training step
 // (direct form: this non-default mode does not use the Winograd / taps-on-N variants).
+// Under --norm batch (kind 1) the norm layers are BatchNorm2d in TRAINING mode on x_hat (the reference calls the module in train
+// mode, loss.py:157-162: the pass updates the running buffers and the counter): ops.h batch_norm_fwd / batch_norm_bwd /
+// batch_norm_bwd2, whose d gamma joins the up pass's gradients; the down pass's batch_norm_bwd adds d gamma / d beta of the injected
+// adjoints.  The convs in front of a norm have no bias there.  Under --norm none (kind 2) every layer is linear or piecewise
+// linear: all injected adjoints are zero, the down pass does not exist, and only the up pass's weight-gradient contractions remain.
 #include <cstring>
 
 #include "engine.h"
@@ -29,9 +34,11 @@ TView flat_view(float* p, size_t n) {
 // n_layers = the PatchGAN's stride-2 levels (define_D's n_layers_D, modules/discriminators.py:110-131): conv k of its
 // nn.Sequential sits at index 0, then 2 + 3 (k - 1) -- [conv, norm, lrelu] triples behind [conv, lrelu]; layers 0 .. n_layers - 1
 // are k4 s2, layer n_layers the k4 s1 conv with a norm, layer n_layers + 1 the k4 s1 prediction conv; norms on 1 .. n_layers.
-GradPenalty::GradPenalty(Ctx& c, ParamArena& arenaD, int B, int H, int W, int n_layers)
-    : ctx_(c), A_(arenaD), B_(B), nl_(n_layers), NL_(n_layers + 2) {
+GradPenalty::GradPenalty(Ctx& c, ParamArena& arenaD, int B, int H, int W, int n_layers, const PatchganNorm& norm)
+    : ctx_(c), A_(arenaD), B_(B), nl_(n_layers), NL_(n_layers + 2), kind_(norm.kind) {
   if (n_layers < 1 || n_layers > 5) throw Error(1, "GradPenalty: n_layers_D must be in [1, 5]");
+  if (kind_ < 0 || kind_ > 2) throw Error(1, "GradPenalty: norm kind must be 0 instance, 1 batch or 2 none");
+  if (kind_ == 1 && !norm.site) throw Error(1, "GradPenalty: batch norm needs the running buffers' owner");
   net_ = std::make_unique<Net>(c, arenaD);
   Net& n = *net_;
   const int nl = nl_, NL = NL_;
@@ -47,24 +54,36 @@ GradPenalty::GradPenalty(Ctx& c, ParamArena& arenaD, int B, int H, int W, int n_
   for (int l = 0; l < NL; ++l) {
     Layer& y = L_[l];
     const ParamDesc& wd = arenaD.params[arenaD.index.at(names[l] + ".weight")];
-    const ParamDesc& bd = arenaD.params[arenaD.index.at(names[l] + ".bias")];
-    y.ws = wd.ws; y.woff = wd.off; y.boff = bd.off;
+    y.ws = wd.ws; y.woff = wd.off;
     y.kind = l < nl ? 0 : 1;
     y.Cin = wd.ws.Cip; y.Co = wd.ws.Co; y.Cop = round_up(wd.ws.Co, 4);
-    y.norm = l >= 1 && l <= nl;
+    const bool site = l >= 1 && l <= nl;              // a norm module's place in the Sequential (Identity under kind 2)
+    y.norm = site && kind_ != 2;
+    y.bias = kind_ == 0 || !site;                     // use_bias is true only under InstanceNorm2d (discriminators.py:104-107)
+    if (y.bias) y.boff = arenaD.params[arenaD.index.at(names[l] + ".bias")].off;
     if (y.kind == 0) { h /= 2; w /= 2; } else { h -= 1; w -= 1; }
     y.h = n.alloc_var(B, h, w, y.Cop, true);
     if (y.norm) {
       y.raw = n.alloc_var(B, h, w, y.Cop, true);
       y.stats = static_cast<float*>(c.alloc((size_t)B * y.Cop * 2 * sizeof(float)));
       y.tmp = n.alloc_var(B, h, w, y.Cop, false).v;
+      if (kind_ == 1) {                               // the norm module is entry K + 1 behind conv model.K
+        const std::string bn = "model." + std::to_string(3 + 3 * (l - 1));
+        if (y.Cop != y.Co) throw Error(1, "GradPenalty: BatchNorm site with padded channels");
+        y.goff = arenaD.params[arenaD.index.at(bn + ".weight")].off;
+        y.beoff = arenaD.params[arenaD.index.at(bn + ".bias")].off;
+        y.fold = static_cast<float*>(c.alloc((size_t)y.Cop * 2 * sizeof(float)));
+        y.run = norm.site(bn, y.Co);
+      }
     }
-    if (l == 0) y.gr0 = n.alloc_var(B, h, w, y.Cop, false).v;
+    if (l == 0 || (site && !y.norm)) y.gr0 = n.alloc_var(B, h, w, y.Cop, false).v;
     if (l < NL - 1) {
       y.u_raw = n.alloc_var(B, h, w, y.Cop, false).v;
       y.u_h = n.alloc_var(B, h, w, y.Cop, false).v;
-      y.a_raw = n.alloc_var(B, h, w, y.Cop, false).v;
-      if (l < nl) y.a_h = n.alloc_var(B, h, w, y.Cop, false).v;
+      if (kind_ != 2) {
+        y.a_raw = n.alloc_var(B, h, w, y.Cop, false).v;
+        if (l < nl) y.a_h = n.alloc_var(B, h, w, y.Cop, false).v;
+      }
     }
     y.dg = static_cast<float*>(c.alloc(dgrad_elems(y.ws, y.kind == 0 ? 0 : 1, y.Cop, y.Cin) * sizeof(float)));
   }
@@ -85,7 +104,7 @@ void GradPenalty::conv(int l, const TView& x, const TView& y, bool bias, int act
   a.g.stride = L.kind == 0 ? 2 : 1;
   a.g.Ho = y.H; a.g.Wo = y.W;
   a.w = A_.w + L.woff; a.Npad = L.ws.Npad;
-  a.bias = bias ? A_.w + L.boff : nullptr;
+  a.bias = bias && L.bias ? A_.w + L.boff : nullptr;
   a.act = act; a.y = y; a.Cout = L.Co;
   conv_fwd(ctx_.s, a);
 }
@@ -102,6 +121,14 @@ void GradPenalty::dgrad(int l, const TView& dy, const TView& dx) {
     d.w = L.dg; d.Npad = L.Cin; d.Cout = L.Cin; d.y = dx;
   }
   conv_fwd(ctx_.s, d);
+}
+// first-order backward through BatchNorm site l; arena != NULL: d gamma / d beta into it
+void GradPenalty::bn_bwd(int l, const TView& dy, const TView& dx, float* arena) {
+  const Layer& L = L_[l];
+  BatchNormBwdArgs b;
+  b.dy = dy; b.x = L.raw.v; b.stats = L.stats; b.fold = L.fold; b.dx = dx; b.groups = 1; b.act = ACT_LRELU;
+  if (arena) { b.dgamma = arena + L.goff; b.dbeta = arena + L.beoff; }
+  batch_norm_bwd(ctx_.s, b);
 }
 void GradPenalty::wgrad(int l, const TView& x, const TView& dy, float* arena) {
   const Layer& L = L_[l];
@@ -140,7 +167,16 @@ void GradPenalty::run(const TView& real, const TView& fake, int gp_mode, float g
   // ---- forward
   conv(0, xh_.v, L_[0].h.v, true, ACT_LRELU);
   for (int l = 1; l <= nl; ++l) {
+    if (kind_ == 2) { conv(l, L_[l - 1].h.v, L_[l].h.v, false, ACT_LRELU); continue; }
     conv(l, L_[l - 1].h.v, L_[l].raw.v, true, ACT_NONE);
+    if (kind_ == 1) {
+      BatchNormArgs a;
+      a.x = L_[l].raw.v; a.y = L_[l].h.v; a.gamma = A_.w + L_[l].goff; a.beta = A_.w + L_[l].beoff;
+      a.running_mean = L_[l].run.mean; a.running_var = L_[l].run.var; a.num_batches_tracked = L_[l].run.count;
+      a.stats = L_[l].stats; a.fold = L_[l].fold; a.groups = 1; a.act = ACT_LRELU; a.training = 1;
+      batch_norm_fwd(s, a);
+      continue;
+    }
     NormActArgs a;
     a.x = L_[l].raw.v; a.y = L_[l].h.v; a.stats = L_[l].stats; a.norm = 1; a.act = ACT_LRELU;
     norm_act_fwd(s, a);
@@ -151,9 +187,17 @@ void GradPenalty::run(const TView& real, const TView& fake, int gp_mode, float g
   wgan_loss(s, pred, 1.f, (float)pred.pixels(), tmp_loss_, &gpred);          // d(sum pred)/d pred = 1 on channel 0
   dgrad(P, gpred, L_[nl].h.g);
   for (int l = nl; l >= 1; --l) {
-    NormActBwdArgs b;
-    b.dy = L_[l].h.g; b.x = L_[l].raw.v; b.stats = L_[l].stats; b.dx = L_[l].raw.g; b.norm = 1; b.act = ACT_LRELU;
-    norm_act_bwd(s, b);
+    if (kind_ == 2) {
+      act_bwd(s, L_[l].h.g, L_[l].h.v, L_[l].gr0, ACT_LRELU, 0);
+      dgrad(l, L_[l].gr0, L_[l - 1].h.g);
+      continue;
+    }
+    if (kind_ == 1) bn_bwd(l, L_[l].h.g, L_[l].raw.g, nullptr);
+    else {
+      NormActBwdArgs b;
+      b.dy = L_[l].h.g; b.x = L_[l].raw.v; b.stats = L_[l].stats; b.dx = L_[l].raw.g; b.norm = 1; b.act = ACT_LRELU;
+      norm_act_bwd(s, b);
+    }
     dgrad(l, L_[l].raw.g, L_[l - 1].h.g);
   }
   act_bwd(s, L_[0].h.g, L_[0].h.v, L_[0].gr0, ACT_LRELU, 0);
@@ -169,22 +213,41 @@ void GradPenalty::run(const TView& real, const TView& fake, int gp_mode, float g
   act_bwd(s, L_[0].u_raw, L_[0].h.v, L_[0].u_h, ACT_LRELU, 0);
   for (int l = 1; l <= nl; ++l) {
     conv(l, L_[l - 1].u_h, L_[l].u_raw, false, ACT_NONE);
+    if (kind_ == 2) {
+      wgrad(l, L_[l - 1].u_h, L_[l].gr0, gA_);
+      act_bwd(s, L_[l].u_raw, L_[l].h.v, L_[l].u_h, ACT_LRELU, 0);
+      continue;
+    }
     wgrad(l, L_[l - 1].u_h, L_[l].raw.g, gA_);
+    if (kind_ == 1) {
+      BatchNormBwd2Args b2;
+      b2.u = L_[l].u_raw; b2.gy = L_[l].h.g; b2.x = L_[l].raw.v; b2.stats = L_[l].stats; b2.fold = L_[l].fold;
+      b2.gamma = A_.w + L_[l].goff; b2.uy = L_[l].u_h; b2.ax = L_[l].a_raw; b2.dgamma = gA_ + L_[l].goff; b2.act = ACT_LRELU;
+      batch_norm_bwd2(s, b2);
+      continue;
+    }
     NormActBwd2Args b2;
     b2.u = L_[l].u_raw; b2.gy = L_[l].h.g; b2.x = L_[l].raw.v; b2.stats = L_[l].stats;
     b2.uy = L_[l].u_h; b2.ax = L_[l].a_raw; b2.act = ACT_LRELU;
     norm_act_bwd2(s, b2);
   }
   wgrad(P, L_[nl].u_h, gpred, gA_);
+  if (kind_ == 2) {          // no norm: every injected adjoint is zero, there is no down pass
+    axpy(s, flat_view(gA_, A_.n), flat_view(A_.g, A_.n), 1.f, 1);
+    return;
+  }
   // ---- down pass of the injected adjoints
   for (int l = nl; l >= 1; --l) {
     wgrad(l, L_[l - 1].h.v, L_[l].a_raw, gB_);
-    bias_grad(s, L_[l].a_raw, gB_ + L_[l].boff);
+    if (L_[l].bias) bias_grad(s, L_[l].a_raw, gB_ + L_[l].boff);
     dgrad(l, L_[l].a_raw, L_[l - 1].a_h);
     if (l - 1 >= 1) {
-      NormActBwdArgs b;
-      b.dy = L_[l - 1].a_h; b.x = L_[l - 1].raw.v; b.stats = L_[l - 1].stats; b.dx = L_[l - 1].tmp; b.norm = 1; b.act = ACT_LRELU;
-      norm_act_bwd(s, b);
+      if (kind_ == 1) bn_bwd(l - 1, L_[l - 1].a_h, L_[l - 1].tmp, gB_);
+      else {
+        NormActBwdArgs b;
+        b.dy = L_[l - 1].a_h; b.x = L_[l - 1].raw.v; b.stats = L_[l - 1].stats; b.dx = L_[l - 1].tmp; b.norm = 1; b.act = ACT_LRELU;
+        norm_act_bwd(s, b);
+      }
       axpy(s, L_[l - 1].tmp, L_[l - 1].a_raw, 1.f, 1);
     } else {
       act_bwd(s, L_[0].a_h, L_[0].h.v, L_[0].a_raw, ACT_LRELU, 0);

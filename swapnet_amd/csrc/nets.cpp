@@ -340,8 +340,9 @@ class WarpModel final : public Model {
   }
   TView output_view() override { return Dx.batch(0, B).v.slice(0, Ccp); }
   int output_channels() const override { return Cc; }
-  // (the reverse-over-reverse pass of gp.cpp walks the n-layer PatchGAN through InstanceNorm)
-  bool supports_gradient_penalty() const override { return d_layers_ >= 1 && d_norm_ == 0; }
+  // (the reverse-over-reverse pass of gp.cpp walks the n-layer PatchGAN through InstanceNorm; through BatchNorm and without a
+  // norm layer in the device library only: batch_norm_bwd2 is a HIP kernel)
+  bool supports_gradient_penalty() const override { return d_layers_ >= 1 && (d_norm_ == 0 || is_device_build()); }
   void forward(bool training, uint64_t seed) override {       // warp_model.py:106-107
     G->training = training; G->seed = seed;
     G->forward();

@@ -344,6 +344,26 @@ struct BatchNormBwdArgs {
   uint64_t salt = 0;
 };
 void batch_norm_bwd(Stream& s, const BatchNormBwdArgs& a);
+// Second-order step through y = act(gamma xh + beta), xh = (x - mean) rstd with the biased statistics of ONE group over N H W
+// (reverse over reverse; the BatchNorm counterpart of norm_act_bwd2 below: the gradient penalties' pass is one B batch).  With
+// z = gamma xh + beta, gm = act'(z) gy, q = gamma gm and <.> the mean over the N H W elements of a channel, the first backward was
+// gx = rstd (q - <q> - xh <q xh>).  Given u, the adjoint of gx:
+//   v  = rstd (u - <u> - xh <u xh>)
+//   uy = act'(z) gamma v                                  (adjoint of gy, and J u for the up pass)
+//   ax = -rstd^2 [ xh (<u q> - <u><q> - <u xh><q xh>) + <q xh> (u - <u> - xh <u xh>) + <u xh> (q - <q> - xh <q xh>) ]
+//   d gamma = sum v gm = rstd M (<u gm> - <u><gm> - <u xh><gm xh>),  M = N H W;   d beta = 0 (piecewise-linear activations)
+// exact with eps inside rstd.  The activation branch is taken from z (with a negative gamma it differs from the sign of xh).  All
+// reductions in fp64 and in a fixed order: two runs are bit-identical.  No dropout variant (the discriminator has none).
+struct BatchNormBwd2Args {
+  TView u, gy, x;             // adjoint of gx; gradient w.r.t. y from the first backward; raw activation
+  const float* stats = nullptr;      // as the training-mode forward left them (groups 1)
+  const float* fold = nullptr;
+  const float* gamma = nullptr;      // [C], 16-byte aligned
+  TView uy, ax;               // outputs (overwritten)
+  float* dgamma = nullptr;    // [C], overwritten; NULL: skipped
+  int act = ACT_NONE;
+};
+void batch_norm_bwd2(Stream& s, const BatchNormBwd2Args& a);
 
 // The keep/scale factor norm_act_fwd / norm_act_bwd apply at a dropout site, written out as an NCHW tensor
 // (N,C,H,W): element (n,c,h,w) = drop_scale(seed, ((n*H*W + h*W + w)*C + c), p) -- 0 or 1/(1-p).

@@ -19,6 +19,13 @@ namespace swn {
 //   e_{d+1} = IN(conv_d(l_d))                   (:247-249)   [innermost: no norm, :232-238]
 //   u_d = IN(convT_d(relu(C_{d+1})))  [+Dropout(0.5) for 4 <= d < depth-1]   (:239-254)
 //   out = tanh(convT_0(relu(C_1)))              (:226-231)
+// --norm (get_norm_layer, modules/__init__.py:53-74) selects the U-Net's norm layer; `encode` = UNetDown(36, 36) hard-codes
+// InstanceNorm2d (modules/layers.py:12-24) and stays as it is.  use_bias is true only under InstanceNorm: under batch / none no
+// U-Net conv carries a bias, the outermost down conv included -- except the outermost ConvTranspose2d, which keeps its default one.
+//   batch (kind 1): every IN above becomes BatchNorm2d (affine, running buffers from site(name, C), one group), the upnorm's
+//                   Dropout fused into its apply pass; names: the block's prefix + .model.2 (downnorm), .model.6 (upnorm;
+//                   innermost .model.4) -- the indexing of unet128_prefix below
+//   none  (kind 2): Identity modules without keys: conv -> LeakyReLU, convT -> [Dropout]
 // ---------------------------------------------------------------------------------------
 static std::string unet_prefix(int d) {
   std::string p = "unet.model";
@@ -27,7 +34,16 @@ static std::string unet_prefix(int d) {
 }
 
 void build_texture_generator(Net& n, const Var& tex, const float* rois_dev, int num_roi, const Var& cloth_slot,
-                             const Var& unet_in, const Var& out, int img_size, int cloth_channels) {
+                             const Var& unet_in, const Var& out, int img_size, int cloth_channels, int norm_kind,
+                             const std::function<Net::BNBuffers(const std::string& name, int C)>& site) {
+  if (norm_kind < 0 || norm_kind > 2) throw Error(1, "TextureModule: norm kind must be 0 instance, 1 batch or 2 none");
+  if (norm_kind == 1 && !site) throw Error(1, "TextureModule: batch norm needs the running buffers' owner");
+  const bool use_bias = norm_kind == 0;
+  // the norm layer + activation [+ Dropout] behind a U-Net conv
+  auto unet_norm = [&](const std::string& name, const Var& raw, const Var& y, int act, float drop) {
+    if (norm_kind == 1) n.batch_norm_act(name, raw, y, act, 1, site(name, raw.v.C), drop);
+    else n.norm_act(raw, y, norm_kind == 0, act, drop);
+  };
   const int B = tex.v.N, H = tex.v.H, W = tex.v.W;
   const int depth = (int)std::lround(std::log2((double)img_size));
   if ((1 << depth) != img_size || H != img_size || W != img_size || depth < 6)
@@ -58,18 +74,18 @@ void build_texture_generator(Net& n, const Var& tex, const float* rois_dev, int 
   }
   // down path
   // (the input gradient is only wanted for the pooled-texture channels: the cloth channels are data)
-  n.conv(unet_prefix(0) + ".model.0", unet_in, C[1].slice(0, 64), CK_K4S2, RC + cloth_channels, 64, true, ACT_LRELU, nullptr, false, RC);
+  n.conv(unet_prefix(0) + ".model.0", unet_in, C[1].slice(0, 64), CK_K4S2, RC + cloth_channels, 64, use_bias, ACT_LRELU, nullptr, false, RC);
   Var innermost_mid;
   for (int d = 1; d < depth; ++d) {
     const int cin = inner(d - 1), cout = inner(d), hw = H >> (d + 1);
     const std::string name = unet_prefix(d) + ".model.1";
     if (d < depth - 1) {
       Var raw = n.alloc_var(B, hw, hw, cout, true);
-      n.conv(name, C[d].slice(0, cin), raw, CK_K4S2, cin, cout, true, ACT_NONE);
-      n.norm_act(raw, C[d + 1].slice(0, cout), true, ACT_LRELU, 0.f);
+      n.conv(name, C[d].slice(0, cin), raw, CK_K4S2, cin, cout, use_bias, ACT_NONE);
+      unet_norm(unet_prefix(d) + ".model.2", raw, C[d + 1].slice(0, cout), ACT_LRELU, 0.f);
     } else {                                      // innermost: conv -> (uprelu) -> convT
       innermost_mid = n.alloc_var(B, hw, hw, cout, true);
-      n.conv(name, C[d].slice(0, cin), innermost_mid, CK_K4S2, cin, cout, true, ACT_RELU);
+      n.conv(name, C[d].slice(0, cin), innermost_mid, CK_K4S2, cin, cout, use_bias, ACT_RELU);
     }
   }
   // up path
@@ -78,9 +94,9 @@ void build_texture_generator(Net& n, const Var& tex, const float* rois_dev, int 
     const bool innermost = d == depth - 1;
     Var raw = n.alloc_var(B, hw, hw, ch, true);
     const std::string name = unet_prefix(d) + (innermost ? ".model.3" : ".model.5");
-    n.convT(name, innermost ? innermost_mid : R[d + 1], raw, ch, true);
+    n.convT(name, innermost ? innermost_mid : R[d + 1], raw, ch, use_bias);
     const float drop = (d >= 4 && d < depth - 1) ? 0.5f : 0.f;
-    n.norm_act(raw, C[d].slice(ch, ch), true, ACT_NONE, drop);
+    unet_norm(unet_prefix(d) + (innermost ? ".model.4" : ".model.6"), raw, C[d].slice(ch, ch), ACT_NONE, drop);
     n.act(C[d], R[d], ACT_RELU);
   }
   Var out_raw = n.alloc_var(B, H, W, 4, true);
@@ -214,10 +230,13 @@ class TextureModel final : public Model {
     ctx = &c; B = B_; H = H_; W = W_; is_train = train; num_roi = nroi;
     Cc = cloth_channels; Ccp = round_up(Cc, 4); RC = 3 * num_roi;
     if (Cc < 1 || Cc > 64) throw Error(1, "TextureModel: cloth_channels in [1,64]");
-    // --norm reaches the texture stage's pix2pix U-Net too (modules/swapnet_modules.py:176-187), which has no BatchNorm / no-norm form
-    if (c.patchgan_norm != 0)
-      throw Error(1, "TextureModel: a non-instance --norm is not implemented for the texture stage (its U-Net generator takes the same "
-                     "norm layer and exists under InstanceNorm only)");
+    // --norm reaches the discriminator and the TextureModule's pix2pix U-Net (modules/swapnet_modules.py:176-187); --netG unet_128
+    // ignores it (texture_model.py:97-101: BatchNorm2d whatever the flag says)
+    const int norm_kind = share ? share->d_norm_ : c.patchgan_norm;
+    if (norm_kind != 0 && !is_device_build())
+      throw Error(1, "TextureModel: a non-instance --norm is not implemented for the texture stage on the host simulator (its U-Net "
+                     "generator takes the same norm layer; BatchNorm / no norm are implemented in the device library only)");
+    d_norm_ = norm_kind;
     if (netG != NETG_SWAPNET && netG != NETG_UNET128) throw Error(1, "TextureModel: netG [" + std::to_string(netG) + "] is not recognized (0 swapnet, 1 unet_128)");
     if (netG == NETG_UNET128 && !is_device_build())
       throw Error(1, "TextureModel: --netG unet_128: BatchNorm is not implemented on the host simulator (HIP kernel only)");
@@ -234,8 +253,10 @@ class TextureModel final : public Model {
     Dx = G->alloc_var(train ? 2 * B : B, H, W, CdB, train);
     rois = static_cast<float*>(c.alloc((size_t)B * num_roi * 4 * sizeof(float)));
     Var fake_slot = Dx.batch(0, B).slice(0, 4);
-    if (netG == NETG_SWAPNET) build_texture_generator(*G, tex, rois, num_roi, unet_in.slice(RC, Ccp), unet_in, fake_slot, H, Cc);
-    else build_unet128_generator(*G, tex, fake_slot, [this](const std::string& name, int C) { return bn_site(name, C, 0); });
+    const auto g_site = [this](const std::string& name, int C) { return bn_site(name, C, 0); };
+    if (netG == NETG_SWAPNET) build_texture_generator(*G, tex, rois, num_roi, unet_in.slice(RC, Ccp), unet_in, fake_slot, H, Cc, norm_kind, g_site);
+    else build_unet128_generator(*G, tex, fake_slot, g_site);
+    if (!train) G->bn_training = false;          // an inference model's BatchNorm sites normalise with the running buffers
     if (!arenaG.frozen) arenaG.allocate(c);
     G->finalize({fake_slot});
     losses = static_cast<float*>(c.alloc(L_COUNT * sizeof(float)));
@@ -246,11 +267,11 @@ class TextureModel final : public Model {
     d_cimap_ = cimap; d_layers_ = c.patchgan_layers;
     D2 = std::make_unique<Net>(c, arenaD);
     D2->keep_wino_inputs = true;
-    pred2 = build_patchgan(*D2, Dx, c.patchgan_layers, cimap);
+    pred2 = build_patchgan(*D2, Dx, c.patchgan_layers, cimap, 0, d_norm(2));          // [fake | real]: one group each
     if (!arenaD.frozen) arenaD.allocate(c);
     D2->finalize({pred2});
     D1 = std::make_unique<Net>(c, arenaD);
-    pred1 = build_patchgan(*D1, Dx.batch(0, B), c.patchgan_layers, cimap, 4);        // d(fakes) only: the condition is data
+    pred1 = build_patchgan(*D1, Dx.batch(0, B), c.patchgan_layers, cimap, 4, d_norm(1));        // d(fakes) only: the condition is data
     D1->finalize({pred1});
     // perceptual network: one instance with gradients (fakes), one without (targets, no_grad :52-53)
     VF = std::make_unique<Net>(c, arenaV);
@@ -395,7 +416,7 @@ class TextureModel final : public Model {
   int output_channels() const override { return 3; }
   void forward(bool training, uint64_t seed) override {        // texture_model.py:121-125
     G->training = training; G->seed = seed;
-    G->bn_training = training;         // (unet_128's BatchNorm sites: nn.Module.train() / eval(); the TextureModule has none)
+    G->bn_training = training;         // (BatchNorm sites -- unet_128's, the TextureModule's under --norm batch: nn.Module.train() / eval())
     G->forward();
     vt_done_ = false;
   }

@@ -211,8 +211,8 @@ class NativeModel:
         return out
 
     def buffer_infos(self, net):
-        """state_dict() buffers of `net` (BatchNorm running statistics: the discriminator under norm="batch", the generator of a
-        texture model with netG="unet_128"): name -> (shape, dtype)."""
+        """state_dict() buffers of `net` (BatchNorm running statistics: the discriminator and the TextureModule's U-Net under
+        norm="batch", the generator of a texture model with netG="unet_128"): name -> (shape, dtype)."""
         n = C.c_int()
         self.lib.call("swn_model_buffer_count", self.handle, net, C.byref(n))
         out = OrderedDict()
@@ -797,6 +797,17 @@ def op_norm_act_bwd2(ctx, x, gy, u, act=1):
     ctx.lib.call("swn_op_norm_act_bwd2", ctx.handle, _C.ptr(d[0]), _C.ptr(d[1]), _C.ptr(d[2]), n, c, h, w, int(act),
                  _C.ptr(uy), _C.ptr(ax))
     return uy, ax
+
+
+def op_batch_norm_act_bwd2(ctx, x, gy, u, weight, bias, act=1):
+    """(uy, ax, dweight) of swn_op_batch_norm_act_bwd2: the second-order step through act(BatchNorm2d(x)) in training mode."""
+    d = [t.to(device=ctx.device, dtype=torch.float32).contiguous() for t in (x, gy, u, weight, bias)]
+    uy, ax = torch.empty_like(d[0]), torch.empty_like(d[0])
+    n, c, h, w = d[0].shape
+    dw = torch.empty(c, dtype=torch.float32, device=ctx.device)
+    ctx.lib.call("swn_op_batch_norm_act_bwd2", ctx.handle, _C.ptr(d[0]), _C.ptr(d[1]), _C.ptr(d[2]), _C.ptr(d[3]), _C.ptr(d[4]),
+                 n, c, h, w, int(act), _C.ptr(uy), _C.ptr(ax), _C.ptr(dw))
+    return uy, ax, dw
 
 
 def op_norm_act_dropout(ctx, x, dy=None, norm=True, act=2, p=0.5, seed=0):

@@ -64,17 +64,18 @@ class BaseGAN(BaseModel, ABC):
         elif self.is_train and getattr(opt, "discriminator", "basic") == "pixel":
             self.backend.n_layers_D = 0             # --discriminator pixel (base_gan.py:61-65): the 1x1 PixelDiscriminator
         norm = getattr(opt, "norm", "instance")
-        if self.is_train and norm != "instance":
+        if norm != "instance" and (self.is_train or self.KIND != "warp"):
             # --norm reaches the discriminator (modules/discriminators.py:77) and the texture stage's U-Net generator
-            # (modules/swapnet_modules.py:176-187); the warp generator hard-codes InstanceNorm.  So the warp stage is complete
-            # with a BatchNorm / no-norm PatchGAN; the texture stage would need the same for its generator.
+            # (modules/swapnet_modules.py:176-187); the warp generator hard-codes InstanceNorm.  BatchNorm and the second-order
+            # pass through it are HIP kernels: the host simulator refuses, stage by stage.
             modules.get_norm_layer(norm)            # unknown names fail like the reference
-            if self.KIND != "warp":
-                raise NotImplementedError("--norm %s is not implemented for the texture stage: the flag also selects the norm layer "
-                                          "of its pix2pix U-Net generator, which exists under instance norm only" % norm)
-            if opt.gan_mode in ("wgan-gp", "dragan-gp", "dragan-lp"):
-                raise NotImplementedError("gan mode %s with --norm %s: the native gradient penalty differentiates twice through "
-                                          "InstanceNorm only" % (opt.gan_mode, norm))
+            if self.KIND != "warp" and not self.backend.ctx.lib.is_device:
+                raise NotImplementedError("--norm %s is not implemented for the texture stage on the host simulator: the flag also "
+                                          "selects the norm layer of its pix2pix U-Net generator, which is implemented under batch / "
+                                          "none in the device library only" % norm)
+            if self.is_train and opt.gan_mode in ("wgan-gp", "dragan-gp", "dragan-lp") and not self.backend.ctx.lib.is_device:
+                raise NotImplementedError("gan mode %s with --norm %s: on the host simulator the native gradient penalty differentiates "
+                                          "twice through InstanceNorm only (BatchNorm / no norm: device library)" % (opt.gan_mode, norm))
             if norm == "batch" and not self.backend.ctx.lib.is_device:
                 raise NotImplementedError("--norm batch: BatchNorm is a HIP kernel only, the host simulator library has none")
             self.backend.norm = norm                # the stage's native networks are built together, on first use

@@ -85,10 +85,10 @@ class Identity(torch.nn.Module):
 
 def get_norm_layer(norm_type="instance"):
     """modules.get_norm_layer (modules/__init__.py:53-74).  The native networks take the layer by name: instance (the reference's
-    default, base_gan.py:72-77), batch (BatchNorm2d, affine, running statistics) or none.  The discriminators implement all
-    three (modules/discriminators.py).  Every generator exists under one layer: WarpModule and TextureModule under instance,
-    the texture stage's plain U-Net (--netG unet_128, modules/pix2pix_modules.UnetGenerator) under batch -- as the reference
-    hard-codes it -- so --norm does not select a generator's layer."""
+    default, base_gan.py:72-77), batch (BatchNorm2d, affine, running statistics) or none.  The discriminators and the
+    TextureModule's U-Net implement all three (batch / none for the texture stage: device library only).  WarpModule exists
+    under instance and the texture stage's plain U-Net (--netG unet_128, modules/pix2pix_modules.UnetGenerator) under batch --
+    as the reference hard-codes them."""
     if norm_type in ("instance", "batch", "none"):
         return norm_type
     raise NotImplementedError("normalization layer [%s] is not found" % norm_type)

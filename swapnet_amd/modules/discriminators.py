@@ -9,11 +9,11 @@ from .native import NativeNet
 def _bind_norm(backend, norm_layer):
     """The discriminator's norm layer (get_norm_layer's name: instance | batch | none) becomes a property of the stage's native
     networks, like n_layers_D.  batch / none: the convs in front of a norm layer have no bias (:104-107,151-154); batch: every norm
-    site owns weight, bias and the running buffers (state-dict keys model.K.* / net.3.*).  Warp stage only: the flag also
-    selects the norm layer of the texture stage's U-Net generator, which exists under instance norm only."""
+    site owns weight, bias and the running buffers (state-dict keys model.K.* / net.3.*).  On the host simulator warp stage only:
+    the flag also selects the norm layer of the texture stage's U-Net generator, which is under batch / none in the device library."""
     if norm_layer not in engine.NORM_KINDS:
         raise NotImplementedError("normalization layer [%s] is not found" % norm_layer)
-    if norm_layer != "instance" and backend.kind != "warp":
+    if norm_layer != "instance" and backend.kind != "warp" and not backend.ctx.lib.is_device:
         raise NotImplementedError("normalization layer [%s] is not implemented for the texture stage: its U-Net generator takes "
                                   "the same norm layer and exists under instance norm only" % norm_layer)
     if backend.models and backend.norm != norm_layer:

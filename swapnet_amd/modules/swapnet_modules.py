@@ -38,13 +38,15 @@ class WarpModule(NativeNet):
 
 class TextureModule(NativeNet):
     """RoIAlign -> UNetDown(36,36) -> nearest upsample -> cat cloth -> pix2pix U-Net
-    (swapnet_modules.py:154-260).  Only the default configuration is native: instance norm,
-    unet_type="pix2pix", depth log2(img_size)."""
+    (swapnet_modules.py:154-260).  unet_type="pix2pix", depth log2(img_size); norm_type selects the U-Net's norm layer
+    (get_norm_layer: instance | batch | none -- `encode` keeps its InstanceNorm): batch and none in the device library only.
+    Under batch / none no U-Net conv but the outermost ConvTranspose2d carries a bias; under batch every norm site has weight,
+    bias and the running buffers in the state dict."""
 
     def __init__(self, texture_channels=3, cloth_channels=19, num_roi=12, norm_type="batch", dropout=0.5,
                  unet_type="pix2pix", img_size=128, backend=None, lib=None):
-        if norm_type != "instance":
-            raise NotImplementedError("normalization layer [%s] is not implemented (instance only)" % norm_type)
+        from . import get_norm_layer
+        norm_type = get_norm_layer(norm_type)                 # unknown names fail like the reference
         if unet_type != "pix2pix":
             raise NotImplementedError("unet_type [%s] is not implemented" % unet_type)
         if texture_channels != 3:
@@ -56,6 +58,12 @@ class TextureModule(NativeNet):
         self.num_downs = math.frexp(img_size)[1] - 1          # swapnet_modules.py:178
         backend = backend or NativeBackend("texture", is_train=False, dropout=dropout, num_roi=num_roi, lib=lib,
                                            default_shape=(1, img_size, img_size), cloth_channels=cloth_channels)
+        if norm_type != "instance" and not backend.ctx.lib.is_device:
+            raise NotImplementedError("normalization layer [%s] is not implemented for the texture stage on the host simulator "
+                                      "(instance only; batch / none: device library only)" % norm_type)
+        if backend.models and backend.norm != norm_type:
+            raise RuntimeError("the stage's networks already exist with norm = %s" % backend.norm)
+        backend.norm = norm_type
         super().__init__(backend, engine.NET_G)
         self.num_roi = num_roi
         self.training = True
