@@ -40,7 +40,8 @@ typedef struct swn_model swn_model;
 
 int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lambda_gp; 4: swn_route_*, swn_model_step_captured, swn_model_create_shared;
                                 5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit; 8: swn_op_loss, swn_op_bias_grad;
-                                9: swn_op_norm_act, swn_op_elementwise, swn_op_resample */
+                                9: swn_op_norm_act, swn_op_elementwise, swn_op_resample (additions since, version unchanged: swn_op_resize_u8,
+                                swn_model_set_input_texture_sources) */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -222,6 +223,16 @@ int swn_model_set_input_labels(swn_model* m, int slot, const int32_t* dev_labels
 int swn_model_set_input_texture_batch(swn_model* m, const uint8_t* img, int b, int hs, int ws, const uint8_t* labels, int hl, int wl,
                                       const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3,
                                       int x_min, int y_min);
+/* Texture models: the same from the DECODED images, each at its own size -- the tf.resize(img, load_size) of
+ * datasets/texture_dataset.py:93-95,132-134 moves into the library.  src = packed device bytes, src_bytes of them; geom_host = HOST
+ * (b,3) int64 rows {byte offset, H0, W0}: sample i is the (H0, W0, 3) uint8 image at src + offset.  Two launches: swn_op_resize_u8
+ * (below: Pillow's bilinear resize, byte for byte) into a (b, hs, ws, 3) buffer the model owns -- allocated when the model is first
+ * used this way, again only if a later call needs a larger one -- then the launch of swn_model_set_input_texture_batch on that
+ * buffer with the remaining arguments unchanged, whose bit-exactness this path inherits.  Every argument of both launches is
+ * checked before the first goes out; the call allocates nothing in steady state and never synchronises. */
+int swn_model_set_input_texture_sources(swn_model* m, const uint8_t* src, size_t src_bytes, const int64_t* geom_host, int b, int hs, int ws,
+                                        const uint8_t* labels, int hl, int wl, const float* rois_raw, int r, const float* sample,
+                                        const float* mean3, const float* std3, int x_min, int y_min);
 /* Warp models: everything swn_model_set_input writes for slots 0 (bodys), 1 (input_cloths) and, when training, 2 (target_cloths) from
  * the COMPACT batch, one device launch (swn_op_warp_batch below has the arithmetic): body (B,hb,wb,3) uint8 = the decoded RGB images,
  * NOT resized; in_labels / tgt_labels (B,hl,wl) uint8 = the cloth label maps as stored (tgt_labels may be the same pointer as
@@ -468,6 +479,25 @@ int swn_op_texture_batch(swn_ctx* ctx, const uint8_t* img, int b, int hs, int ws
                          const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3, int x_min,
                          int y_min, int h, int w, int cloth_channels, float* in_nchw, float* tgt_nchw, float* cloths_nchw,
                          float* rois_out);
+/* tf.resize(img, load_size) of TextureDataset.__getitem__ (datasets/texture_dataset.py:93-95,132-134) = Pillow's
+ * Image.resize((ws, hs), Image.BILINEAR) on RGB uint8, for a batch of images of DIFFERENT sizes as ONE device launch, byte for byte
+ * (Pillow's 8-bit resample; no box, no reducing_gap).  src = packed device bytes; geom_host = HOST (b,3) int64 rows {byte offset, H0,
+ * W0}; dst = device (b,hs,ws,3) uint8, dense.  Per axis, source length `in`, output length `out`, in IEEE double, one rounded
+ * operation per step, no fused multiply-add:
+ *   scale = (double)in / out;  fs = max(scale, 1.0);  support = 1.0 * fs;  ss = 1.0 / fs
+ *   for each output index xx:
+ *     center = (xx + 0.5) * scale
+ *     xmin = (int)(center - support + 0.5), at least 0;  xmax = (int)(center + support + 0.5), at most in;  n = xmax - xmin
+ *     w[x] = tri((x + xmin - center + 0.5) * ss) for x = 0 .. n-1,  tri(a) = |a| < 1 ? 1 - |a| : 0
+ *     ww = w[0] + w[1] + ... in index order;  w[x] /= ww if ww != 0;  k[x] = (int)(0.5 + w[x] * 4194304.0)      22 fractional bits
+ *   one pass, per output element and colour byte:  dst = clamp((2097152 + sum_x src[xmin + x] * k[x]) >> 22, 0, 255)     in int32
+ * If ws != W0 the horizontal pass runs first and leaves ROUNDED bytes (H0, ws); if hs != H0 the vertical pass runs on those.  An
+ * axis whose length does not change is not resampled; both equal: a copy.  Every sample is validated before anything is
+ * launched: H0, W0 >= 1, offset + 3 * H0 * W0 <= src_bytes (samples may overlap), and BOUND: H0 <= 31 * hs and W0 <= 31 * ws (windows
+ * of at most 63 taps; a larger reduction is refused by name).  The kernel cannot read outside [src, src + src_bytes).  Enqueued on
+ * the context's stream: no device allocation, no synchronisation; geom_host is consumed before the call returns.  On the simulator
+ * src and dst are host pointers. */
+int swn_op_resize_u8(swn_ctx* ctx, const uint8_t* src, size_t src_bytes, const int64_t* geom_host, int b, int hs, int ws, uint8_t* dst);
 /* WarpDataset.__getitem__ (datasets/warp_dataset.py:139-183) for a whole batch as ONE device launch, from the compact form
  * (arguments as swn_model_set_input_warp_batch; h x w = the crop window at (x_min, y_min) of the load_size x load_size resized sample).
  * With (y, x) a pixel of the window, sy = y_min + y, sx = x_min + x, Ls = load_size and

@@ -64,6 +64,8 @@ _PROTOS = {
     "swn_model_set_input": ([_vp, _i, _fp, _i, _i, _i, _i], _i),
     "swn_model_set_input_labels": ([_vp, _i, _vp, _i, _i, _i], _i),
     "swn_model_set_input_texture_batch": ([_vp, _vp, _i, _i, _i, _vp, _i, _i, _fp, _i, _fp, C.POINTER(_f), C.POINTER(_f), _i, _i], _i),
+    "swn_model_set_input_texture_sources": ([_vp, _vp, C.c_size_t, _vp, _i, _i, _i, _vp, _i, _i, _fp, _i, _fp, C.POINTER(_f), C.POINTER(_f),
+                                             _i, _i], _i),
     "swn_model_set_input_warp_batch": ([_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, C.POINTER(_f), C.POINTER(_f), _i, _i, _i], _i),
     "swn_model_get_output": ([_vp, _i, _fp], _i),
     "swn_model_get_tap": ([_vp, _i, C.c_char_p, _fp, C.POINTER(_i * 4)], _i),
@@ -116,6 +118,7 @@ _PROTOS = {
     "swn_op_affine_gather": ([_vp, _fp, _fp, _i, _i, _i, _i, _vp, _i], _i),
     "swn_op_texture_batch": ([_vp, _vp, _i, _i, _i, _vp, _i, _i, _fp, _i, _fp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i,
                              _fp, _fp, _fp, _fp], _i),
+    "swn_op_resize_u8": ([_vp, _vp, C.c_size_t, _vp, _i, _i, _i, _vp], _i),
     "swn_op_warp_batch": ([_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i, _i,
                           _fp, _fp, _fp], _i),
     "swn_op_gan_loss": ([_vp, _i, _fp, _i, _i, _i, _i, _f, _i, _f, _fp, _fp], _i),

@@ -382,6 +382,14 @@ int swn_model_set_input_texture_batch(swn_model* m, const uint8_t* img, int b, i
     m->m->set_input_texture_batch(img, b, hs, ws, labels, hl, wl, rois_raw, r, sample, mean3, std3, x_min, y_min);
   });
 }
+int swn_model_set_input_texture_sources(swn_model* m, const uint8_t* src, size_t src_bytes, const int64_t* geom_host, int b, int hs, int ws,
+                                        const uint8_t* labels, int hl, int wl, const float* rois_raw, int r, const float* sample,
+                                        const float* mean3, const float* std3, int x_min, int y_min) {
+  return guard([&] {
+    REQUIRE(m && src && geom_host && labels && rois_raw && sample && mean3 && std3, "NULL argument");
+    m->m->set_input_texture_sources(src, src_bytes, geom_host, b, hs, ws, labels, hl, wl, rois_raw, r, sample, mean3, std3, x_min, y_min);
+  });
+}
 int swn_model_set_input_warp_batch(swn_model* m, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels,
                                    const uint8_t* tgt_labels, int hl, int wl, const double* maps, int nmaps, const float* mean3,
                                    const float* std3, int load_size, int x_min, int y_min) {
@@ -940,6 +948,14 @@ int swn_op_texture_batch(swn_ctx* ctx, const uint8_t* img, int b, int hs, int ws
     nhwc_to_nchw(tmp.s, a.tgt_tex, tgt_nchw, 3);
     nhwc_to_nchw(tmp.s, a.cloth[0], cloths_nchw, cloth_channels);
     stream_sync(tmp.s);
+  });
+}
+int swn_op_resize_u8(swn_ctx* ctx, const uint8_t* src, size_t src_bytes, const int64_t* geom_host, int b, int hs, int ws, uint8_t* dst) {
+  return guard([&] {
+    REQUIRE(ctx && src && geom_host && dst, "NULL argument");
+    ResizeU8Args a;
+    a.src = src; a.src_bytes = src_bytes; a.geom = geom_host; a.B = b; a.Hs = hs; a.Ws = ws; a.dst = dst;
+    resize_u8(ctx->c->s, a);                 // enqueued only: no allocation, no synchronisation
   });
 }
 int swn_op_warp_batch(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int hl,

@@ -1593,6 +1593,10 @@ void Model::set_input_texture_batch(const uint8_t*, int, int, int, const uint8_t
                                     const float*, int, int) {
   throw Error(1, "set_input_texture_batch: only the texture model takes a texture batch");
 }
+void Model::set_input_texture_sources(const uint8_t*, size_t, const int64_t*, int, int, int, const uint8_t*, int, int, const float*, int,
+                                      const float*, const float*, const float*, int, int) {
+  throw Error(1, "set_input_texture_sources: only the texture model takes a texture batch");
+}
 void Model::set_input_warp_batch(const uint8_t*, int, int, int, const uint8_t*, const uint8_t*, int, int, const double*, int, const float*,
                                  const float*, int, int, int) {
   throw Error(1, "set_input_warp_batch: only the warp model takes a warp batch");
@@ -1875,6 +1879,86 @@ __attribute__((weak)) void warp_batch(Stream&, const WarpBatchArgs& a) {
           if (src >= 0 && a.in_labels[lb + src] == c) dst[c] = 1.f;
         }
       }
+  }
+}
+
+// Host form of Pillow's bilinear resize (ops.h resize_u8), weak like texture_batch above: the same expressions in the same order as
+// image_resize.hip, whole images instead of tiles.
+__attribute__((weak)) void resize_u8(Stream&, const ResizeU8Args& a) {
+  resize_u8_check(a);
+  struct Axis { std::vector<int> kmin, kn, k; int ksize = 1; };
+  auto tri = [](double v) { if (v < 0.0) v = -v; return v < 1.0 ? 1.0 - v : 0.0; };
+  // (volatile: one rounded double operation per step, whatever the compiler's contraction rules)
+  auto windows = [&](int in, int out) {
+    Axis ax;
+    ax.kmin.resize(out); ax.kn.resize(out);
+    if (in == out) {                                           // not resampled: the identity window returns the byte exactly
+      ax.k.assign(out, 1 << 22);
+      for (int xx = 0; xx < out; ++xx) { ax.kmin[xx] = xx; ax.kn[xx] = 1; }
+      return ax;
+    }
+    volatile double scale = (double)in / (double)out;
+    const double fs = scale < 1.0 ? 1.0 : (double)scale;
+    volatile double support = 1.0 * fs;
+    volatile double ss = 1.0 / fs;
+    ax.ksize = 2 * RESIZE_MAX_FACTOR + 2;
+    ax.k.assign((size_t)out * ax.ksize, 0);
+    for (int xx = 0; xx < out; ++xx) {
+      volatile double center = ((double)xx + 0.5) * scale;
+      volatile double lo = center - support;
+      volatile double hi = center + support;
+      int xmin = (int)(lo + 0.5);
+      if (xmin < 0) xmin = 0;
+      int xmax = (int)(hi + 0.5);
+      if (xmax > in) xmax = in;
+      const int n = std::min(xmax - xmin, ax.ksize);
+      int* k = ax.k.data() + (size_t)xx * ax.ksize;
+      volatile double ww = 0.0;
+      for (int x = 0; x < n; ++x) {
+        volatile double d = (double)(x + xmin) - center;
+        volatile double e = d + 0.5;
+        volatile double arg = e * ss;
+        ww = ww + tri(arg);
+      }
+      for (int x = 0; x < n; ++x) {
+        volatile double d = (double)(x + xmin) - center;
+        volatile double e = d + 0.5;
+        volatile double arg = e * ss;
+        volatile double w = tri(arg);
+        if (ww != 0.0) w = w / ww;
+        volatile double q = w * 4194304.0;
+        k[x] = (int)(0.5 + q);
+      }
+      ax.kmin[xx] = xmin; ax.kn[xx] = n;
+    }
+    return ax;
+  };
+  auto clip8 = [](int acc) { const int v = acc >> 22; return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); };
+  std::vector<uint8_t> inter;
+  for (int b = 0; b < a.B; ++b) {
+    const int H0 = (int)a.geom[3 * b + 1], W0 = (int)a.geom[3 * b + 2];
+    const uint8_t* im = a.src + a.geom[3 * b];
+    uint8_t* out = a.dst + (size_t)b * a.Hs * a.Ws * 3;
+    const Axis hx = windows(W0, a.Ws), vx = windows(H0, a.Hs);
+    inter.resize((size_t)H0 * a.Ws * 3);
+    for (int y = 0; y < H0; ++y)                               // horizontal pass: rounded bytes (H0, Ws)
+      for (int x = 0; x < a.Ws; ++x)
+        for (int c = 0; c < 3; ++c) {
+          const uint8_t* sp = im + ((size_t)y * W0 + hx.kmin[x]) * 3 + c;
+          const int* k = hx.k.data() + (size_t)x * hx.ksize;
+          int acc = 1 << 21;
+          for (int i = 0; i < hx.kn[x]; ++i) acc += (int)sp[(size_t)i * 3] * k[i];
+          inter[((size_t)y * a.Ws + x) * 3 + c] = clip8(acc);
+        }
+    const size_t rowlen = (size_t)a.Ws * 3;
+    for (int y = 0; y < a.Hs; ++y) {                           // vertical pass on those
+      const int* k = vx.k.data() + (size_t)y * vx.ksize;
+      for (size_t j = 0; j < rowlen; ++j) {
+        int acc = 1 << 21;
+        for (int i = 0; i < vx.kn[y]; ++i) acc += (int)inter[(size_t)(vx.kmin[y] + i) * rowlen + j] * k[i];
+        out[(size_t)y * rowlen + j] = clip8(acc);
+      }
+    }
   }
 }
 

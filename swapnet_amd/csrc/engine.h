@@ -430,6 +430,11 @@ class Model {
   virtual void set_input_texture_batch(const uint8_t* img, int N, int Hs, int Ws, const uint8_t* labels, int Hl, int Wl,
                                        const float* rois_raw, int R, const float* sample, const float mean[3], const float std_[3],
                                        int x_min, int y_min);
+  // the same from the DECODED images, each at its own size: Pillow's bilinear resize to Hs x Ws (ops.h resize_u8; src packed bytes,
+  // geom_host (N,3) = offset, H0, W0) into a buffer this model owns, then set_input_texture_batch on it -- two launches
+  virtual void set_input_texture_sources(const uint8_t* src, size_t src_bytes, const int64_t* geom_host, int N, int Hs, int Ws,
+                                         const uint8_t* labels, int Hl, int Wl, const float* rois_raw, int R, const float* sample,
+                                         const float mean[3], const float std_[3], int x_min, int y_min);
   // warp models: every buffer set_input fills for slots 0-2 from the compact batch in one launch (ops.h warp_batch); the crop window is
   // the model's H x W at (x_min, y_min) of the load_size x load_size resized sample; tgt_labels may be in_labels, NULL for inference
   virtual void set_input_warp_batch(const uint8_t* body, int N, int Hb, int Wb, const uint8_t* in_labels, const uint8_t* tgt_labels,

@@ -1,7 +1,7 @@
 // swapnet_amd -- device op launchers.  The engine (engine.cpp) is written against this
 // header only.  The product implementation is the set of HIP translation units in this
 // directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, batch_norm.hip, losses.hip, optim.hip, gather.hip,
-// texture_batch.hip, warp_batch.hip).
+// texture_batch.hip, warp_batch.hip, image_resize.hip).
 // tests/hostsim/hostsim_ops.cpp implements the same signatures with plain loops so that
 // the engine's graph / backward / packing logic can be checked in CI without a GPU; it is
 // never part of the shipped library.
@@ -462,6 +462,49 @@ inline void texture_batch_check(const TextureBatchArgs& a) {
   if (a.tgt_tex.p && (!tileable(a.tgt_tex) || a.tgt_tex.C != 4 || !same(a.tgt_tex))) throw Error(1, "texture_batch tgt_tex: view mismatch");
   for (int k = 0; k < a.ncloth; ++k)
     if (!tileable(a.cloth[k]) || a.cloth[k].C != round_up(a.C, 4) || !same(a.cloth[k])) throw Error(1, "texture_batch cloth: view mismatch");
+}
+
+// ---- Pillow's bilinear resize of uint8 RGB images (image_resize.hip) -----------------------------------------------------------
+// Image.resize((Ws, Hs), Image.BILINEAR) of the reference's tf.resize(img, load_size) (datasets/texture_dataset.py:93-95,132-134)
+// for a batch of decoded images of DIFFERENT sizes in one launch, byte for byte: Pillow's 8-bit resample (Resample.c), no box, no
+// reducing_gap.  Per axis with source length `in` and output length `out`, in IEEE double, one rounded operation per step:
+//   scale = (double)in / out;  fs = max(scale, 1.0);  support = 1.0 * fs;  ss = 1.0 / fs
+//   center = (xx + 0.5) * scale
+//   xmin = (int)(center - support + 0.5), at least 0;  xmax = (int)(center + support + 0.5), at most in;  n = xmax - xmin
+//   w[x] = tri((x + xmin - center + 0.5) * ss), tri(a) = |a| < 1 ? 1 - |a| : 0;  ww = w[0] + w[1] + ... in index order;
+//   w[x] /= ww where ww != 0;  k[x] = (int)(0.5 + w[x] * 4194304.0)                                    (22 fractional bits)
+//   dst = clamp((2097152 + sum_x src[xmin + x] * k[x]) >> 22, 0, 255)                                   (int32)
+// The horizontal pass runs first where Ws != W0 and leaves ROUNDED bytes (H0, Ws); the vertical pass runs on those where Hs != H0.  An
+// axis whose length does not change is not resampled (here: the identity coefficients xmin = xx, n = 1, k = 1 << 22, which give
+// the source byte back exactly).
+// src: packed bytes; sample b is the (H0, W0, 3) image at byte `offset`, geom[b] = {offset, H0, W0} -- a HOST array, validated before
+// anything is launched.  dst: (B, Hs, Ws, 3) dense.  BOUND: in <= 31 * out on both axes (windows of at most 63 taps: the
+// coefficient and intermediate-row stages of a workgroup are static LDS); a larger reduction is refused by name.
+constexpr int RESIZE_MAX_FACTOR = 31;
+struct ResizeU8Args {
+  const uint8_t* src = nullptr; size_t src_bytes = 0;
+  const int64_t* geom = nullptr;                             // HOST (B,3): byte offset, H0, W0
+  int B = 0, Hs = 0, Ws = 0;
+  uint8_t* dst = nullptr;                                    // (B,Hs,Ws,3)
+};
+void resize_u8(Stream& s, const ResizeU8Args& a);
+// the argument checks of every resize_u8 implementation (the HIP launcher and the host loop of engine.cpp): after it, no sample
+// reaches outside [src, src + src_bytes) and every window fits the kernel's stages
+inline void resize_u8_check(const ResizeU8Args& a) {
+  if (!a.src || !a.geom || !a.dst) throw Error(1, "resize_u8: NULL argument");
+  if (a.B < 1 || a.Hs < 1 || a.Ws < 1) throw Error(1, "resize_u8: empty sizes");
+  for (int b = 0; b < a.B; ++b) {
+    const int64_t off = a.geom[3 * b], h0 = a.geom[3 * b + 1], w0 = a.geom[3 * b + 2];
+    const std::string who = "resize_u8: sample " + std::to_string(b);
+    if (h0 < 1 || w0 < 1 || h0 > 0x7fffffff || w0 > 0x7fffffff)
+      throw Error(1, who + " has an empty or oversized source (H0 " + std::to_string(h0) + ", W0 " + std::to_string(w0) + ")");
+    const uint64_t bytes = 3ull * (uint64_t)h0 * (uint64_t)w0;           // < 3 * 2^62: no wrap
+    if (off < 0 || (uint64_t)off > a.src_bytes || bytes > a.src_bytes - (uint64_t)off)
+      throw Error(1, who + " runs past src_bytes (offset " + std::to_string(off) + " + " + std::to_string(bytes) + " > " + std::to_string(a.src_bytes) + ")");
+    if (h0 > (int64_t)RESIZE_MAX_FACTOR * a.Hs || w0 > (int64_t)RESIZE_MAX_FACTOR * a.Ws)
+      throw Error(1, who + " exceeds the reduction bound: " + std::to_string(h0) + " x " + std::to_string(w0) + " -> " + std::to_string(a.Hs) +
+                         " x " + std::to_string(a.Ws) + " is more than " + std::to_string(RESIZE_MAX_FACTOR) + " to 1 on an axis");
+  }
 }
 
 // ---- warp batch hand-over (warp_batch.hip) ------------------------------------------------------------------------------------

@@ -390,9 +390,38 @@ class TextureModel final : public Model {
   // slots 0-3 from the compact batch, one launch (ops.h texture_batch) instead of the six of the calls above
   void set_input_texture_batch(const uint8_t* img, int N, int Hs, int Ws, const uint8_t* labels, int Hl, int Wl, const float* rois_raw,
                                int R, const float* sample, const float mean[3], const float std_[3], int x_min, int y_min) override {
+    const TextureBatchArgs a = texture_batch_args(img, N, Hs, Ws, labels, Hl, Wl, rois_raw, R, sample, mean, std_, x_min, y_min);
+    vt_done_ = false;
+    texture_batch(ctx->s, a);
+  }
+  // the same from the decoded images: Pillow's resize (ops.h resize_u8) into resized_, then the hand-over above on it.  Both
+  // launches' arguments are checked before the first one goes out.
+  uint8_t* resized_ = nullptr; size_t resized_bytes_ = 0;
+  void set_input_texture_sources(const uint8_t* src, size_t src_bytes, const int64_t* geom_host, int N, int Hs, int Ws,
+                                 const uint8_t* labels, int Hl, int Wl, const float* rois_raw, int R, const float* sample,
+                                 const float mean[3], const float std_[3], int x_min, int y_min) override {
+    if (N != B) throw Error(1, "set_input_texture_sources: shape mismatch with the model's batch");
+    if (Hs < 1 || Ws < 1) throw Error(1, "set_input_texture_sources: empty resized size");
+    ResizeU8Args ra;
+    ra.src = src; ra.src_bytes = src_bytes; ra.geom = geom_host; ra.B = N; ra.Hs = Hs; ra.Ws = Ws;
+    const size_t need = (size_t)N * Hs * Ws * 3;
+    if (need > resized_bytes_) {                               // once per model, unless a later batch asks for a larger resized size
+      AllocScope mine(*ctx, owned_allocs);
+      resized_ = static_cast<uint8_t*>(ctx->alloc(need));
+      resized_bytes_ = need;
+    }
+    ra.dst = resized_;
+    resize_u8_check(ra);
+    const TextureBatchArgs a = texture_batch_args(resized_, N, Hs, Ws, labels, Hl, Wl, rois_raw, R, sample, mean, std_, x_min, y_min);
+    texture_batch_check(a);
+    resize_u8(ctx->s, ra);
+    vt_done_ = false;
+    texture_batch(ctx->s, a);
+  }
+  TextureBatchArgs texture_batch_args(const uint8_t* img, int N, int Hs, int Ws, const uint8_t* labels, int Hl, int Wl, const float* rois_raw,
+                                      int R, const float* sample, const float mean[3], const float std_[3], int x_min, int y_min) {
     if (N != B) throw Error(1, "set_input_texture_batch: shape mismatch with the model's batch");
     if (R != num_roi) throw Error(1, "rois must be (B, num_roi, 4)");
-    vt_done_ = false;
     TextureBatchArgs a;
     a.img = img; a.Hs = Hs; a.Ws = Ws; a.labels = labels; a.Hl = Hl; a.Wl = Wl; a.rois_raw = rois_raw; a.R = R; a.sample = sample;
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std_[c]; }
@@ -406,7 +435,7 @@ class TextureModel final : public Model {
       a.tgt_tex = Dx.batch(B, B).v.slice(0, 4);
     }
     a.rois_out = rois;
-    texture_batch(ctx->s, a);
+    return a;
   }
   void get_output(int slot, float* dst) override {
     if (slot != 0) throw Error(1, "get_output: unknown slot");

@@ -373,6 +373,34 @@ class NativeModel:
             self.ctx.consumed(token)
         self._keep = dev
 
+    def set_input_texture_sources(self, batch):
+        """Texture model: every input slot from the sources form of GpuTextureBatch.collate -- `sources_u8` (the decoded images,
+        packed back to back), `source_geom` (B,3) int64 {offset, H0, W0}, `resized` (Hs, Ws) and the label maps, ROIs and scalars of
+        the compact batch -- in two device launches: Pillow's bilinear resize (swn_op_resize_u8), then the compact hand-over."""
+        specs = (("sources_u8", torch.uint8), ("cloth_labels_u8", torch.uint8), ("rois_raw", torch.float32), ("sample_params", torch.float32))
+        dev, tokens = [], []
+        for name, dtype in specs:
+            t, token = self.ctx.upload(torch.as_tensor(batch[name]), dtype, key=(id(self), "ts", name))
+            dev.append(t); tokens.append(token)
+        src, lab, rois, sample = dev
+        geom = _source_geom(batch["source_geom"])
+        b = geom.shape[0]
+        if src.dim() != 1 or lab.dim() != 3 or rois.dim() != 3 or rois.shape[2] != 4 or tuple(sample.shape) != (b, 5):
+            raise ValueError("texture sources: sources_u8 (bytes,), source_geom (B,3), cloth_labels_u8 (B,Hl,Wl), rois_raw (B,R,4), sample_params (B,5)")
+        if lab.shape[0] != b or rois.shape[0] != b:
+            raise ValueError("texture sources: the batch sizes of its tensors differ")
+        hs, ws = (int(v) for v in batch["resized"])
+        mean, std = batch["norm_stats"]
+        x_min, y_min = batch["crop"][:2]
+        self._torch_done()
+        self.lib.call("swn_model_set_input_texture_sources", self.handle, _C.ptr(src), C.c_size_t(src.numel()), _C.ptr(geom), b, hs, ws,
+                      _C.ptr(lab), lab.shape[1], lab.shape[2], _C.ptr(rois), rois.shape[1], _C.ptr(sample),
+                      (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(x_min), int(y_min))
+        self._sync_if_needed()
+        for token in tokens:
+            self.ctx.consumed(token)
+        self._keep = dev
+
     def set_input_warp_batch(self, batch):
         """Warp model: bodys, input_cloths and (training) target_cloths from the compact batch dict of
         datasets.gpu_warp_batch.GpuWarpBatch.collate (uint8 body images and label maps, the per-channel map table) in one device
@@ -648,6 +676,50 @@ def op_texture_batch(ctx, textures_u8, labels_u8, rois_raw, sample_params, mean,
                  _C.ptr(rois), rois.shape[1], _C.ptr(sample), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(x_min), int(y_min),
                  int(height), int(width), int(cloth_channels), _C.ptr(inp), _C.ptr(tgt), _C.ptr(cloths), _C.ptr(out))
     return inp, tgt, cloths, out
+
+
+def _source_geom(geom):
+    """(B,3) int64 {byte offset, H0, W0} as a contiguous HOST tensor (the library reads it before the call returns)."""
+    g = torch.as_tensor(geom).to(device="cpu", dtype=torch.int64).contiguous()
+    if g.dim() != 2 or g.shape[1] != 3 or g.shape[0] < 1:
+        raise ValueError("resize_u8: the geometry must be (B, 3) rows {offset, H0, W0}, got %s" % (tuple(g.shape),))
+    return g
+
+
+def pack_u8_images(images):
+    """HWC uint8 RGB images of any sizes -> (their bytes back to back, 1-D uint8; (B,3) int64 rows {byte offset, H0, W0})."""
+    flat, rows, off = [], [], 0
+    for a in images:
+        t = torch.as_tensor(a)
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError("resize_u8: images must be (H0, W0, 3) uint8, got %s %s" % (tuple(t.shape), t.dtype))
+        flat.append(t.contiguous().reshape(-1))
+        rows.append((off, t.shape[0], t.shape[1]))
+        off += t.numel()
+    if not flat:
+        raise ValueError("resize_u8: an empty list of images")
+    return torch.cat(flat), torch.tensor(rows, dtype=torch.int64)
+
+
+def op_resize_u8_packed(ctx, packed_u8, geom, hs, ws):
+    """swn_op_resize_u8 on an already packed byte buffer and its (B,3) geometry: (B, hs, ws, 3) uint8 on the context's device."""
+    src = torch.as_tensor(packed_u8).to(device=ctx.device, dtype=torch.uint8).contiguous()
+    g = _source_geom(geom)
+    if src.dim() != 1:
+        raise ValueError("resize_u8: the packed source must be one-dimensional")
+    dst = torch.empty((g.shape[0], int(hs), int(ws), 3), dtype=torch.uint8, device=ctx.device)
+    if ctx.owns_stream:                     # (the upload above ran on torch's stream)
+        torch.cuda.current_stream(ctx.device).synchronize()
+    ctx.lib.call("swn_op_resize_u8", ctx.handle, _C.ptr(src), C.c_size_t(src.numel()), _C.ptr(g), g.shape[0], int(hs), int(ws), _C.ptr(dst))
+    if ctx.owns_stream:                     # (... and the caller reads dst on it)
+        ctx.sync()
+    return dst
+
+
+def op_resize_u8(ctx, images, hs, ws):
+    """Pillow's Image.resize((ws, hs), Image.BILINEAR) of a list of (H0, W0, 3) uint8 images, each at its own size, in one device
+    launch (swn_op_resize_u8), byte for byte: a (B, hs, ws, 3) uint8 tensor on the context's device."""
+    return op_resize_u8_packed(ctx, *pack_u8_images(images), hs, ws)
 
 
 AMAX_SLOT = 256                     # floats of one amax slot (ops.h)

@@ -139,11 +139,16 @@ class TextureModel(BaseGAN):
     del _lazy
 
     def _set_input_compact(self, input):
-        """The compact batch of datasets.gpu_texture_batch.GpuTextureBatch.collate: every slot in one device launch."""
-        B = input["textures_u8"].shape[0]
+        """The compact batch of datasets.gpu_texture_batch.GpuTextureBatch.collate: every slot in one device launch; in its sources
+        form (decoded images at their own sizes) Pillow's resize runs on the device first, a second launch."""
+        from_sources = "sources_u8" in input
+        B = len(input["source_geom"]) if from_sources else input["textures_u8"].shape[0]
         _, _, W, H = input["crop"]
         m = self.backend.ensure(B, H, W)
-        m.set_input_texture_batch(input)
+        if from_sources:
+            m.set_input_texture_sources(input)
+        else:
+            m.set_input_texture_batch(input)
         self._compact = input
         self.textures = self.cloths = self.targets = None
         self.rois = input["rois_raw"]
@@ -152,7 +157,7 @@ class TextureModel(BaseGAN):
 
     def set_input(self, input):
         """texture_model.py:113-119."""
-        if "textures_u8" in input:
+        if "textures_u8" in input or "sources_u8" in input:
             return self._set_input_compact(input)
         self._compact = None
         self.textures, self.rois, self.cloths = input["input_textures"], input["rois"], input["cloths"]
