@@ -41,7 +41,7 @@ typedef struct swn_model swn_model;
 int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lambda_gp; 4: swn_route_*, swn_model_step_captured, swn_model_create_shared;
                                 5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit; 8: swn_op_loss, swn_op_bias_grad;
                                 9: swn_op_norm_act, swn_op_elementwise, swn_op_resample (additions since, version unchanged: swn_op_resize_u8,
-                                swn_model_set_input_texture_sources) */
+                                swn_model_set_input_texture_sources, swn_op_conv_views) */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -580,6 +580,40 @@ int swn_op_elementwise(swn_ctx* ctx, int op, const float* a, const float* b, int
  * lead_pad[6] = a, b, out; accumulate (ops 1, 3, 4) and slot (ops 0, 2) as in swn_op_elementwise. */
 int swn_op_resample(swn_ctx* ctx, int op, const float* a, const float* b, int n, int c, int h, int w, int factor, int accumulate,
                     const int* lead_pad, float* out, float* slot, uint8_t* pattern, float* out_buf);
+/* swn_op_conv on views, as the networks call their convolutions (tests): the same kind 0..5, transposed, what 0 / 1 / 2, naive and
+ * NCHW tensors of the LOGICAL channels, with the conventions of the three entry points above.  x and y are each a slice of a parent
+ * Var (value and gradient buffers of one geometry): the parent has lead_c + C + pad_c channels and n_lead + n + n_pad images, C =
+ * round_up(ci, 4) (x; cimap_len with a channel map) or round_up(co, 4) (y), and the conv gets parent.batch(n_lead, n).slice(lead_c, C).
+ * views = host int[8]: {lead_c, pad_c, n_lead, n_pad} of x, then of y; lead_c, pad_c multiples of 4.  Every byte of the four parent
+ * buffers (x, x.g, y, y.g) holds 0x7f before the logical channels are loaded; the channels INSIDE a view that are not logical -- at
+ * and above ci / co, or with map entry -1 -- are loaded with zeros in all four, as the allocator and the producers leave them in a
+ * network.  What is not loaded keeps the sentinel (y and y.g of a forward call, x.g of an overwriting input-gradient call, ...).
+ * what 0: x, wgt, bias in, y out.  what 1: x in, y = dY in, wgt = weights in (a forward pass in front runs on them) and dW out.
+ * what 2: y = dY in, wgt in, x = dX out, all ci logical channels of the view x.g (those a narrow gradient leaves alone come back as
+ * they were loaded).  act may be LeakyReLU or ReLU in the backward calls too (tanh in the forward call only): the forward pass then
+ * runs first on x (an input of what 2 as well) and the weights, dY is the gradient of the ACTIVATED output, and y_fwd (optional)
+ * receives that forward output (n, co, Ho, Wo), from which a reference takes the branch pattern.
+ * cimap (optional, host, cimap_len entries, one per view channel of x): view channel -> logical channel or -1 = layout pad; ci must
+ * be the number of non-negative entries.  cimap, x_is_input and dgrad_C are handed to the layer unchanged (not with transposed).
+ * operand_slots != 0: the value buffer of x and the gradient buffer of y get external amax slots, taken over the loaded VIEWS, as a model
+ * gives the buffers it fills from outside the tape; the launches then take the slot-scaled and pair-form routes of a training step
+ * (swn_op_conv_produced).  0: every launch takes the amax of its operand itself, with a pass over the view.
+ * dx_old (optional, what 2, (n, ci, h, w)): x.g is loaded with it and x is announced to the accumulate planner as a gradient that
+ * exists already, so that the planner sets the layer's accumulate flag: the flag reaches the kernels in no other way.  pre_range
+ * (optional, host int[2] = {c0, c}): channels [c0, c0 + c) of x's PARENT gradient buffer are announced as existing too; a range that
+ * covers part of the view makes planning fail ("partially initialised gradient range").
+ * y_slot (optional): the 256 floats of the amax slot of y's buffer after the forward pass; an error where the layer's route leaves
+ * no complete slot (it does for a direct conv with fused LeakyReLU / ReLU) and in a backward call that runs no forward pass.
+ * dw_rows (optional, what 1): the packed weight gradient with EVERY row of the view, (co, C, KH, KW) (transposed: (C, co, 4, 4)):
+ * rows of non-logical channels included.  x_buf, xg_buf, y_buf, yg_buf (optional): each whole parent buffer afterwards,
+ * (n_lead + n + n_pad, lead_c + C + pad_c, H, W).
+ * What tests/test_conv_views.py holds every route to: nothing outside a view is written (lead / pad channels and images keep
+ * 0x7f7f7f7f; the channels of x.g at and above a narrow gradient's dgrad_C keep what they held); the non-logical channels inside
+ * the views of y and x.g are exactly 0 afterwards; dw_rows is exactly 0 in the rows of non-logical channels; two runs are bit-equal. */
+int swn_op_conv_views(swn_ctx* ctx, int kind, int transposed, int what, int naive, float* x, int n, int ci, int h, int w, float* wgt,
+                      int co, const float* bias, int act, float* y, const int* views, const int32_t* cimap, int cimap_len,
+                      int x_is_input, int dgrad_C, int operand_slots, const float* dx_old, const int* pre_range, float* y_fwd,
+                      float* y_slot, float* dw_rows, float* x_buf, float* xg_buf, float* y_buf, float* yg_buf);
 /* torch.optim.AdamW single step on flat arrays (optimizers/__init__.py:52-59) */
 int swn_op_adamw(swn_ctx* ctx, float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2,
                  float eps, float wd, int step);

@@ -128,6 +128,8 @@ _PROTOS = {
                          _fp, _fp, _fp, _fp, _fp, _vp, C.POINTER(_i), _fp, _fp, _fp], _i),
     "swn_op_elementwise": ([_vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_i), _fp, _fp, _fp], _i),
     "swn_op_resample": ([_vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), _fp, _fp, _vp, _fp], _i),
+    "swn_op_conv_views": ([_vp, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _fp, _i, _fp, C.POINTER(_i), C.POINTER(C.c_int32), _i, _i, _i, _i,
+                           _fp, C.POINTER(_i), _fp, _fp, _fp, _fp, _fp, _fp, _fp], _i),
     "swn_op_norm_act_bwd2": ([_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp], _i),
     "swn_op_batch_norm_act_bwd2": ([_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp], _i),
     "swn_op_norm_act_dropout": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, C.c_uint64, _fp, _fp, _fp], _i),

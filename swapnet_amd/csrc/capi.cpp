@@ -1207,6 +1207,164 @@ int swn_op_resample(swn_ctx* ctx, int op, const float* a, const float* b, int n,
     stream_sync(s);
   });
 }
+// ---- one convolution on views, as the networks call it (swapnet_hip.h: swn_op_conv_views) ----
+namespace {
+// one operand of swn_op_conv_views: value and gradient parents of (n_lead + n + n_pad) x H x W x (lead + cv + pad), every byte the
+// sentinel, and the view parent.batch(n_lead, n).slice(lead, cv) the conv gets
+struct ConvOperand { Var parent, view; };
+ConvOperand conv_operand(Net& net, Stream& s, int n, int h, int w, int cv, const int* g) {
+  REQUIRE(g[0] >= 0 && g[1] >= 0 && g[0] % 4 == 0 && g[1] % 4 == 0, "lead_c and pad_c must be non-negative multiples of 4");
+  REQUIRE(g[2] >= 0 && g[3] >= 0, "n_lead and n_pad must be non-negative");
+  ConvOperand o;
+  o.parent = net.alloc_var(g[2] + n + g[3], h, w, g[0] + cv + g[1], true);
+  for (const TView* t : {&o.parent.v, &o.parent.g}) dev_memset(s, t->p, kPadSentinelByte, t->pixels() * t->cs * sizeof(float));
+  o.view = o.parent.batch(g[2], n).slice(g[0], cv);
+  return o;
+}
+// channel j of image i of a view, as a 1 x H x W x 1 view
+TView plane_of(const TView& v, int i, int j) {
+  TView r = v;
+  r.p = v.p + (size_t)i * v.H * v.W * v.cs + j;
+  r.N = 1; r.C = 1;
+  return r;
+}
+// Loads a view: its non-logical channels (map entry -1, or at and above c_log without a map) with zeros, its logical channels with
+// nchw (n, c_log, h, w), or leaves them as they are (nchw == NULL).  zeros = n * H * W device zeros.
+void view_load(Stream& s, const TView& v, const float* nchw, int c_log, const std::vector<int32_t>& map, const float* zeros) {
+  const size_t hw = (size_t)v.H * v.W;
+  for (int j = 0; j < v.C; ++j) {
+    const int src = map.empty() ? (j < c_log ? j : -1) : map[j];
+    if (src < 0) { nchw_to_nhwc(s, zeros, v.N, 1, v.H, v.W, v.slice(j, 1)); continue; }
+    if (!nchw || map.empty()) continue;
+    for (int i = 0; i < v.N; ++i) nchw_to_nhwc(s, nchw + ((size_t)i * c_log + src) * hw, 1, 1, v.H, v.W, plane_of(v, i, j));
+  }
+  if (nchw && map.empty()) nchw_to_nhwc(s, nchw, v.N, c_log, v.H, v.W, v);
+}
+void view_store(Stream& s, const TView& v, float* nchw, int c_log, const std::vector<int32_t>& map) {
+  if (map.empty()) { nhwc_to_nchw(s, v, nchw, c_log); return; }
+  const size_t hw = (size_t)v.H * v.W;
+  for (int j = 0; j < v.C; ++j)
+    if (map[j] >= 0)
+      for (int i = 0; i < v.N; ++i) nhwc_to_nchw(s, plane_of(v, i, j), nchw + ((size_t)i * c_log + map[j]) * hw, 1);
+}
+}  // namespace
+int swn_op_conv_views(swn_ctx* ctx, int kind, int transposed, int what, int naive, float* x, int n, int ci, int h, int w, float* wgt,
+                      int co, const float* bias, int act, float* y, const int* views, const int32_t* cimap, int cimap_len,
+                      int x_is_input, int dgrad_C, int operand_slots, const float* dx_old, const int* pre_range, float* y_fwd,
+                      float* y_slot, float* dw_rows, float* x_buf, float* xg_buf, float* y_buf, float* yg_buf) {
+  return guard([&] {
+    REQUIRE(ctx && x && wgt && y && views, "NULL argument");
+    REQUIRE(kind >= 0 && kind <= 5 && what >= 0 && what <= 2, "bad kind/what");
+    REQUIRE(n > 0 && ci > 0 && co > 0 && h > 0 && w > 0, "bad shape");
+    REQUIRE(act >= ACT_NONE && act <= ACT_TANH, "bad activation");
+    REQUIRE(what == 0 || act != ACT_TANH, "no network takes a gradient through a fused tanh");
+    REQUIRE(!transposed || (act == ACT_NONE && !cimap && !x_is_input && dgrad_C == 0), "a transposed conv has no fused activation, channel map or first-layer option");
+    REQUIRE(!dx_old || what == 2, "dx_old belongs to the input-gradient call");
+    REQUIRE(!dw_rows || what == 1, "dw_rows belongs to the weight-gradient call");
+    REQUIRE(!y_fwd || (what != 0 && act != ACT_NONE), "y_fwd: the forward output of a backward call with a fused activation");
+    std::vector<int32_t> map;
+    if (cimap) {
+      REQUIRE(cimap_len > 0 && cimap_len % 4 == 0, "cimap: one entry per view channel of x (a multiple of 4)");
+      map.assign(cimap, cimap + cimap_len);
+      std::vector<char> seen(ci, 0);
+      int logical = 0;
+      for (int32_t m : map) {
+        REQUIRE(m >= -1 && m < ci, "cimap: entries are -1 or a logical channel");
+        if (m >= 0) { REQUIRE(!seen[m], "cimap: a logical channel appears twice"); seen[m] = 1; ++logical; }
+      }
+      REQUIRE(logical == ci, "cimap: ci must be the number of non-negative entries");
+    }
+    struct Restore { ~Restore() { conv_force_naive(0); } } restore;
+    conv_force_naive(naive);
+    Ctx tmp(ctx->c->s);
+    ParamArena A;
+    Net net(tmp, A);
+    Stream& s = tmp.s;
+    const int Cip = cimap ? cimap_len : round_up(ci, 4), Cop = round_up(co, 4);
+    int Ho, Wo;
+    if (transposed) { Ho = 2 * h; Wo = 2 * w; }
+    else if (kind == CK_K4S2) { Ho = h / 2; Wo = w / 2; }
+    else if (kind == CK_K4S1) { Ho = h - 1; Wo = w - 1; }
+    else if (kind == CK_TAIL_UP) { Ho = 2 * h; Wo = 2 * w; }
+    else { Ho = h; Wo = w; }
+    REQUIRE(Ho > 0 && Wo > 0, "the map is too small for this conv");
+    ConvOperand xo = conv_operand(net, s, n, h, w, Cip, views), yo = conv_operand(net, s, n, Ho, Wo, Cop, views + 4);
+    const Var &xv = xo.view, &yv = yo.view;
+    if (transposed) { REQUIRE(Cip == ci, "transposed conv needs Ci % 4 == 0"); net.convT("l", xv, yv, co, bias != nullptr); }
+    else net.conv("l", xv, yv, (ConvKind)kind, ci, co, bias != nullptr, act, cimap ? &map : nullptr, x_is_input != 0, dgrad_C);
+    A.allocate(tmp);
+    // the accumulate flag reaches the kernels through the planner alone, as in a model: x.g holds a gradient already (dx_old), and
+    // optionally a further channel range of x's parent does
+    std::vector<Var> pre;
+    if (dx_old) pre.push_back(xv);
+    if (pre_range) {
+      REQUIRE(pre_range[0] >= 0 && pre_range[1] > 0 && pre_range[0] + pre_range[1] <= xo.parent.g.C, "pre_range: {c0, c} within x's parent buffer");
+      pre.push_back(xo.parent.slice(pre_range[0], pre_range[1]));
+    }
+    net.finalize(pre);
+    // operand_slots: x and dY get the external amax slots a model gives the buffers it fills from outside the tape, and the launches
+    // take the slot-scaled / pair-form routes of a training step; without, every launch takes the amax of its operand itself
+    float* op_slots = nullptr;
+    if (operand_slots) {
+      op_slots = static_cast<float*>(tmp.alloc(2 * AMAX_SLOT * sizeof(float)));
+      dev_memset(s, op_slots, 0, 2 * AMAX_SLOT * sizeof(float));
+      net.set_external_slot(xv.vbase, op_slots);
+      net.set_external_slot(yv.gbase, op_slots + AMAX_SLOT);
+    }
+    const ParamDesc& wd = A.params[A.index.at("l.weight")];
+    const std::vector<int32_t> no_map;
+    const size_t zn = (size_t)n * std::max(h * w, Ho * Wo);
+    float* zeros = static_cast<float*>(tmp.alloc(zn * sizeof(float)));
+    dev_memset(s, zeros, 0, zn * sizeof(float));
+    const bool fwd_first = what != 0 && act != ACT_NONE;
+    view_load(s, xv.v, (what != 2 || fwd_first) ? x : nullptr, ci, map, zeros);
+    view_load(s, xv.g, dx_old, ci, map, zeros);
+    view_load(s, yv.v, nullptr, co, no_map, zeros);
+    view_load(s, yv.g, what != 0 ? y : nullptr, co, no_map, zeros);
+    if (op_slots && (what != 2 || fwd_first)) tensor_amax(s, xv.v, op_slots);
+    if (op_slots && what != 0) tensor_amax(s, yv.g, op_slots + AMAX_SLOT);
+    pack_weight(s, wd.ws, wgt, A.w + wd.off);       // (what 1: the forward pass in front of the backward one runs on them)
+    if (bias) dev_copy(s, A.w + A.params[A.index.at("l.bias")].off, bias, co * sizeof(float));
+    auto copy_slot = [&] {
+      if (!y_slot) return;
+      auto it = net.buf_slots.find(yv.vbase);
+      if (it == net.buf_slots.end() || !it->second.complete || !net.amax) throw Error(1, "swn_op_conv_views: y has no complete amax slot on this route");
+      dev_copy(s, y_slot, net.amax + it->second.off, AMAX_SLOT * sizeof(float));
+    };
+    if (what == 0) {
+      net.forward();
+      nhwc_to_nchw(s, yv.v, y, co);
+      copy_slot();
+    } else {
+      REQUIRE(!y_slot || fwd_first, "y_slot: the backward calls run the forward pass only in front of a fused activation");
+      if (fwd_first) {
+        net.forward();
+        if (y_fwd) nhwc_to_nchw(s, yv.v, y_fwd, co);
+        copy_slot();
+      }
+      if (what == 1) {
+        net.refresh_dgrad();
+        net.backward(true, false);
+        unpack_weight(s, wd.ws, A.g + wd.off, wgt);
+        if (dw_rows) {            // every packed row, the non-logical ones included: (co, Cip, KH, KW) / transposed (Cip, co, 4, 4)
+          WShape all = wd.ws;
+          all.Ci = all.Cip; all.cimap = nullptr;
+          unpack_weight(s, all, A.g + wd.off, dw_rows);
+        }
+      } else {
+        A.version += 1;
+        net.refresh_dgrad();
+        net.backward(false, true);
+        view_store(s, xv.g, x, ci, map);
+      }
+    }
+    if (x_buf) nhwc_to_nchw(s, xo.parent.v, x_buf, xo.parent.v.C);
+    if (xg_buf) nhwc_to_nchw(s, xo.parent.g, xg_buf, xo.parent.g.C);
+    if (y_buf) nhwc_to_nchw(s, yo.parent.v, y_buf, yo.parent.v.C);
+    if (yg_buf) nhwc_to_nchw(s, yo.parent.g, yg_buf, yo.parent.g.C);
+    stream_sync(s);
+  });
+}
 int swn_op_norm_act_bwd2(swn_ctx* ctx, const float* x, const float* gy, const float* u, int n, int c, int h, int w, int act,
                          float* uy, float* ax) {
   return guard([&] {

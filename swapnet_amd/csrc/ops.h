@@ -91,6 +91,14 @@ bool slot_audit_on();
 
 // ---- implicit-GEMM convolution (MFMA) -----------------------------------------------
 // y[map(m)][co] (=|+=) act( sum_k A[m][k] * w[k][co] + bias[co] ),  A = gather(x)
+// Views and pad channels (tests/test_conv_views.py asserts every line of this, per kernel route, through swn_op_conv_views): x, y and
+// dy are channel-slice views (cs >= C, any base offset, a run of the parent's images) and every route -- the launches below, the
+// Winograd transforms and adjoints, the amax passes in front of and behind them -- reads and writes channels [0, C) of the view's
+// pixels and nothing else of the buffer.  The channels of a view at and above the layer's logical count (x.C > Ci, y.C = round_up(Cout,
+// 4) > Cout) and the layout pads of a channel map hold zeros on entry; a launch leaves them alone or writes zeros into them (adds zero
+// when it accumulates), so they are exactly 0 afterwards, and the weight-gradient rows of such input channels are exactly 0.  With
+// accumulate the launch adds to what the view holds; an input gradient formed for the first dgrad_C channels only leaves the others
+// as they were.  The order of every sum is fixed by the shape: two runs give bit-equal results.
 struct ConvFwdArgs {
   TView x;
   Gather g;

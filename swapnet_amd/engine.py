@@ -815,6 +815,72 @@ def op_resample(ctx, op, a, b=None, factor=2, accumulate=False, old=None, views=
     return out, slot, pat, buf
 
 
+def conv_out_hw(kind, transposed, h, w):
+    """Output map of a conv kind (include/swapnet_hip.h swn_op_conv) on an h x w input."""
+    if transposed or kind == 4:
+        return 2 * h, 2 * w
+    return {0: (h // 2, w // 2), 2: (h - 1, w - 1)}.get(kind, (h, w))
+
+
+def op_conv_views(ctx, kind, transposed, what, x, wgt, dy=None, bias=None, act=0, naive=False, views=None, cimap=None, x_is_input=False,
+                  dgrad_C=0, operand_slots=False, dx_old=None, pre_range=None, want_slot=False):
+    """One convolution on views through swn_op_conv_views (include/swapnet_hip.h): views = {"x" | "y": (lead_c, pad_c, n_lead, n_pad)}.
+    x (N, Ci, H, W) and wgt are the LOGICAL tensors ((Co, Ci, k, k); transposed (Ci, Co, 4, 4)); x is the forward input (what 0 / 1,
+    and what 2 behind a fused activation; zeros will do where the call does not read it), dy the gradient of the (activated) output
+    for what 1 / 2.  cimap: one entry per view channel of x (-1 = layout pad).  operand_slots: x and dy get external amax slots (the
+    routes of a training step).  dx_old: the gradient x.g holds already (what 2; the planner then accumulates).  pre_range = (c0, c):
+    a further channel range of x's parent gradient buffer announced to the planner as existing.
+    Returns a dict: "out" (y / dW / dX), "y_fwd" (backward calls behind an activation), "y_slot" (want_slot), "dw_rows" (what 1: all
+    packed rows), and the four whole parent buffers "x_buf", "xg_buf", "y_buf", "yg_buf"."""
+    f32 = dict(dtype=torch.float32, device=ctx.device)
+    wd = _dev(ctx, wgt)
+    co = wd.shape[1] if transposed else wd.shape[0]
+    ci = wd.shape[0] if transposed else wd.shape[1]
+    k = wd.shape[2]
+    n, h, w = x.shape[0], x.shape[2], x.shape[3]          # (x gives the input shape: zeros will do where the call does not read it)
+    if x.shape[1] != ci:
+        raise ValueError("op_conv_views: x has %d channels, the weights %d" % (x.shape[1], ci))
+    ho, wo = conv_out_hw(kind, transposed, h, w)
+    names = ("x", "y")
+    views = views or {}
+    if set(views) - set(names):
+        raise ValueError("unknown operand(s) %s (have %s)" % (sorted(set(views) - set(names)), list(names)))
+    geo = {k_: tuple(int(v) for v in views.get(k_, (0, 0, 0, 0))) for k_ in names}
+    va = (C.c_int * 8)(*(geo["x"] + geo["y"]))
+    cm, cv = None, -(-ci // 4) * 4
+    if cimap is not None:
+        cv = len(cimap)
+        cm = (C.c_int32 * cv)(*[int(v) for v in cimap])
+    cov = -(-co // 4) * 4
+    xd = _dev(ctx, x).clone()
+    bd = _dev(ctx, bias)
+    fwd_first = what != 0 and act != 0
+    if what == 0:
+        yd = torch.empty((n, co, ho, wo), **f32)
+    else:
+        yd = _dev(ctx, dy).clone()
+        if tuple(yd.shape) != (n, co, ho, wo):
+            raise ValueError("op_conv_views: dy must be %s, got %s" % ((n, co, ho, wo), tuple(yd.shape)))
+    if what == 1:
+        wd = wd.clone()
+    old = _dev(ctx, dx_old)
+    pr = (C.c_int * 2)(*[int(v) for v in pre_range]) if pre_range is not None else None
+
+    def whole(g, c, hh, ww):
+        return torch.empty((g[2] + n + g[3], g[0] + c + g[1], hh, ww), **f32)
+    r = {"y_fwd": torch.empty((n, co, ho, wo), **f32) if fwd_first else None,
+         "y_slot": torch.empty(AMAX_SLOT, **f32) if want_slot else None,
+         "dw_rows": torch.empty((cv, co, 4, 4) if transposed else (co, cv, k, k), **f32) if what == 1 else None,
+         "x_buf": whole(geo["x"], cv, h, w), "xg_buf": whole(geo["x"], cv, h, w),
+         "y_buf": whole(geo["y"], cov, ho, wo), "yg_buf": whole(geo["y"], cov, ho, wo)}
+    ctx.lib.call("swn_op_conv_views", ctx.handle, int(kind), int(bool(transposed)), int(what), int(bool(naive)), _C.ptr(xd), n, ci, h, w,
+                 _C.ptr(wd), co, _C.ptr(bd), int(act), _C.ptr(yd), va, cm, cv if cm is not None else 0, int(bool(x_is_input)), int(dgrad_C),
+                 int(bool(operand_slots)), _C.ptr(old), pr, _C.ptr(r["y_fwd"]), _C.ptr(r["y_slot"]), _C.ptr(r["dw_rows"]), _C.ptr(r["x_buf"]), _C.ptr(r["xg_buf"]),
+                 _C.ptr(r["y_buf"]), _C.ptr(r["yg_buf"]))
+    r["out"] = {0: yd, 1: wd, 2: xd}[what]
+    return r
+
+
 def _warp_maps(maps, b, cloth_channels):
     """The map table of a warp batch as a (b * cloth_channels, nmaps, 9) float64 tensor and nmaps; (None, 0) without augmentation."""
     if maps is None:
