@@ -288,6 +288,22 @@ int swn_pipeline_create(swn_model* warp, swn_model* texture, swn_pipeline** out)
 int swn_pipeline_destroy(swn_pipeline* p);
 int swn_pipeline_run(swn_pipeline* p, int use_graph, int* graph_replayed);
 int swn_pipeline_labels(swn_pipeline* p, int32_t** dev_labels);   /* (B,H,W) int32 of the last run, library-owned */
+/* The images inference.py saves per sample (inference.py:94-126: get_current_visuals + save_images, i.e. datasets/data_utils.py:41-90
+ * unnormalize / scale_tensor(scale_each), util/decode_labels.py:24-55, util/draw_rois.py:16-47, util/util.py:9-32 tensor2im) produced
+ * on the device as the tail of the sequence -- seven launches of swn_op_image_u8's kernels, INSIDE the captured graph -- instead
+ * of fp32 read-backs and host loops.  body_* / tex_* = --body_norm_stats / --texture_norm_stats, colours = (num_roi, 3) outline bytes,
+ * all HOST arrays; width = outline width in pixels (util/draw_rois.py:41: int(round(0.01 * W))).  reference_quirk != 0 reproduces
+ * unnormalize's zip over dim 0 (see swn_op_image_u8), 0 un-normalises every image per channel.  All images use tensor2im's
+ * [-1,1] -> [0,255] mapping, as the reference's do.  Allocates the sheet; a graph captured earlier is dropped, so the next
+ * swn_pipeline_run(use_graph) runs eagerly and captures again, the one after replays.  May be called again (new tables).  RGB bodies,
+ * at most 16 ROIs.  Without this call the pipeline enqueues exactly what it did before the call existed. */
+int swn_pipeline_enable_images(swn_pipeline* p, const float* body_mean3, const float* body_std3, const float* tex_mean3,
+                               const float* tex_std3, const uint8_t* colours, int width, int reference_quirk);
+/* The sheet of the last run: *dev = library-owned device bytes (K,B,H,W,3), *k = K = 6, in the order inputs_decoded (the warp
+ * stage's input cloth: argmax of the staged one-hot map, which is the staged label map), bodys_unnormalized, fakes_decoded (from
+ * swn_pipeline_labels' map; also the texture stage's cloths_decoded, whose cloth input is that map), textures_unnormalized with the
+ * ROI outlines, fakes, fakes_scaled.  Stream-ordered behind the run: synchronise (swn_ctx_sync) before reading. */
+int swn_pipeline_images(swn_pipeline* p, uint8_t** dev, int* k);
 
 /* Data-parallel texture stage: the style term is MSE(Gram(output), Gram(target)) with the Gram over the WHOLE batch viewed
  * as (B*C, H*W) (modules/losses/perceptual.py:6-10,58-63), so it couples the samples of all ranks.  The host all-gathers the
@@ -392,6 +408,24 @@ int swn_op_roi_align_indices(swn_ctx* ctx, const float* rois, int k, int h, int 
                              uint8_t* valid);
 /* util.decode_labels.decode_cloth_labels (util/decode_labels.py:24-55): (B,C,H,W) f32 -> (B,3,H,W) u8 */
 int swn_op_decode_labels(swn_ctx* ctx, const float* x, int b, int c, int h, int w, uint8_t* rgb);
+/* util.tensor2im (util/util.py:9-32) for a whole batch, with what the reference runs in front of it folded in: out (B,H,W,3) uint8,
+ * interleaved, what Image.fromarray takes.  All pointers but ctx are device pointers.
+ *   source 0 (float):  x (B,C,H,W) NCHW, C = 3, or 1 replicated to three (util/util.py:24-25);
+ *   source 1 (argmax): x (B,C,H,W), C label channels; the first maximum selects one of the 19 colours of util/decode_labels.py:8-21;
+ *   source 2 (labels): x NULL, labels (B,H,W) int32 select the colour.  A label outside [0,19) gives black.  Palette sources write
+ *     the palette's bytes (the reference's tensor2im of decode_cloth_labels' uint8 tensor wraps modulo 256: not reproduced).
+ *   rows (float source, or NULL): [B][2C+1] = scale[C], shift[C], clamp flag per image: u = v * scale + shift, two rounded fp32
+ *     operations, then clamp to [0,1] if the flag is non-zero -- unnormalize (datasets/data_utils.py:41-58), which zips over dim 0:
+ *     image b < 3 gets (std[b], mean[b]) on all channels and is clamped, later images are left alone (scale 1, shift 0, flag 0).
+ *   scale_each != 0 (float source, excludes rows): scale_tensor(scale_each=True) (datasets/data_utils.py:61-90): lo / hi = min / max of
+ *     image b, u = (clamp(v, lo, hi) + (-lo)) / (float)((double)hi - (double)lo + 1e-5), reduced on the device.
+ *   range 0: byte = (u + 1) / 2 * 255 (tensor2im; the reference applies it to its [0,1] visuals as well); 1: byte = u * 255.  Both
+ *     saturate to [0,255] and truncate: numpy's cast wherever that is defined.  NaN in a float source: unspecified bytes.
+ *   rois (B,R,4) = x0,y0,x1,y1, R <= 16 (0: none), colours (R,3) uint8, width >= 1: draw_rois_on_texture (util/draw_rois.py:16-47):
+ *     a pixel takes the colour of the last ROI whose outline covers it, by Pillow's ImageDraw.rectangle(outline, width) rule
+ *     (coordinates truncated toward zero, clipped to the image).  x1 < x0 or y1 < y0 is Pillow's ValueError: check before calling. */
+int swn_op_image_u8(swn_ctx* ctx, const float* x, int b, int c, int h, int w, const int32_t* labels, int source, const float* rows,
+                    int scale_each, int range, const float* rois, int r, const uint8_t* colours, int width, uint8_t* out);
 /* datasets/data_utils.py:322 (argmax for compress_and_save_cloth) and :330-343 (to_onehot_tensor) */
 int swn_op_argmax_labels(swn_ctx* ctx, const float* x, int b, int c, int h, int w, int32_t* labels);
 int swn_op_labels_to_onehot(swn_ctx* ctx, const int32_t* labels, int b, int c, int h, int w, float* out);

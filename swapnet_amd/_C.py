@@ -78,6 +78,9 @@ _PROTOS = {
     "swn_pipeline_destroy": ([_vp], _i),
     "swn_pipeline_run": ([_vp, _i, C.POINTER(_i)], _i),
     "swn_pipeline_labels": ([_vp, C.POINTER(_vp)], _i),
+    "swn_pipeline_enable_images": ([_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(C.c_uint8), _i, _i], _i),
+    "swn_pipeline_images": ([_vp, C.POINTER(_vp), C.POINTER(_i)], _i),
+    "swn_op_image_u8": ([_vp, _fp, _i, _i, _i, _i, _vp, _i, _fp, _i, _i, _fp, _i, _vp, _i, _vp], _i),
     "swn_model_set_style_context": ([_vp, _fp, _fp, _i, _i], _i),
     "swn_model_set_gp_random": ([_vp, _fp, _fp], _i),
     "swn_model_discriminate": ([_vp, _fp, _fp], _i),

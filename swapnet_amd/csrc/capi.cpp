@@ -512,6 +512,20 @@ int swn_pipeline_run(swn_pipeline* p, int use_graph, int* graph_replayed) {
 int swn_pipeline_labels(swn_pipeline* p, int32_t** dev_labels) {
   return guard([&] { REQUIRE(p && dev_labels, "NULL argument"); *dev_labels = p->p->labels(); });
 }
+int swn_pipeline_enable_images(swn_pipeline* p, const float* body_mean3, const float* body_std3, const float* tex_mean3,
+                               const float* tex_std3, const uint8_t* colours, int width, int reference_quirk) {
+  return guard([&] {
+    REQUIRE(p && body_mean3 && body_std3 && tex_mean3 && tex_std3 && colours, "NULL argument");
+    p->p->enable_images(body_mean3, body_std3, tex_mean3, tex_std3, colours, width, reference_quirk != 0);
+  });
+}
+int swn_pipeline_images(swn_pipeline* p, uint8_t** dev, int* k) {
+  return guard([&] {
+    REQUIRE(p && dev && k, "NULL argument");
+    REQUIRE(p->p->images(), "swn_pipeline_images: the pipeline was not armed (swn_pipeline_enable_images)");
+    *dev = p->p->images(); *k = Pipeline::IMAGE_SHEETS;
+  });
+}
 int swn_model_forward(swn_model* m, int training, uint64_t seed) {
   return guard([&] { REQUIRE(m, "NULL"); m->m->forward(training != 0, seed); });
 }
@@ -616,6 +630,30 @@ int swn_op_decode_labels(swn_ctx* ctx, const float* x, int b, int c, int h, int 
     Var t = net.alloc_var(b, h, w, round_up(c, 4), false);
     nchw_to_nhwc(tmp.s, x, b, c, h, w, t.v);
     decode_labels(tmp.s, t.v, c, rgb);
+    stream_sync(tmp.s);
+  });
+}
+int swn_op_image_u8(swn_ctx* ctx, const float* x, int b, int c, int h, int w, const int32_t* labels, int source, const float* rows,
+                    int scale_each, int range, const float* rois, int r, const uint8_t* colours, int width, uint8_t* out) {
+  return guard([&] {
+    REQUIRE(ctx && out, "NULL argument");
+    REQUIRE(b > 0 && h > 0 && w > 0, "image_u8: empty sizes");
+    REQUIRE(source == SRC_LABELS ? (labels && !x) : (x && !labels), "image_u8: x for the float and argmax sources, labels (and a NULL x) for SRC_LABELS");
+    Ctx tmp(ctx->c->s);
+    ParamArena A; Net net(tmp, A);
+    ImageU8Args a;
+    a.source = source; a.rows = rows; a.scale_each = scale_each; a.range = range; a.rois = rois; a.R = r; a.colours = colours; a.width = width;
+    a.out = out;
+    if (source == SRC_LABELS) {
+      a.labels = labels; a.B = b; a.H = h; a.W = w;
+    } else {
+      REQUIRE(c >= 1 && c <= 256, "image_u8: 1 to 256 channels");
+      Var t = net.alloc_var(b, h, w, round_up(c, 4), false);        // pad channels zero: a 3-in-4 view, as the models hold theirs
+      nchw_to_nhwc(tmp.s, x, b, c, h, w, t.v);
+      a.x = t.v; a.C = c;
+      if (scale_each) a.minmax = static_cast<float*>(tmp.alloc((size_t)b * image_u8_chunks(h, w) * 2 * sizeof(float)));
+    }
+    image_u8(tmp.s, a);
     stream_sync(tmp.s);
   });
 }

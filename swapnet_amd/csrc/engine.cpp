@@ -1962,4 +1962,75 @@ __attribute__((weak)) void resize_u8(Stream&, const ResizeU8Args& a) {
   }
 }
 
+// Host form of the saved-image visuals (ops.h image_u8), weak like texture_batch above: the same expressions in the same order as
+// image_out.hip, whole images instead of four-pixel groups; the min / max of scale_each is taken in place (the scratch is not used).
+__attribute__((weak)) void image_u8(Stream&, const ImageU8Args& args) {
+  const ImageU8Args a = image_u8_check(args);
+  static const uint8_t palette[LABEL_PALETTE_SIZE][3] = {SWN_LABEL_PALETTE};
+  const int HW = a.H * a.W, w = a.width;
+  // (volatile: one rounded fp32 operation per step, whatever the compiler's contraction rules)
+  auto to_byte = [&](float u) {
+    float t;
+    if (a.range == RANGE_SIGNED) { volatile float s1 = u + 1.f; volatile float h = s1 / 2.f; volatile float m = h * 255.f; t = m; }
+    else { volatile float m = u * 255.f; t = m; }
+    return (uint8_t)(int)std::fmin(std::fmax(t, 0.f), 255.f);
+  };
+  for (int b = 0; b < a.B; ++b) {
+    float lo = INFINITY, hi = -INFINITY, den = 1.f;
+    if (a.scale_each) {
+      for (int p = 0; p < HW; ++p)
+        for (int c = 0; c < a.C; ++c) { const float v = a.x.p[((size_t)b * HW + p) * a.x.cs + c]; lo = std::fmin(lo, v); hi = std::fmax(hi, v); }
+      den = (float)((double)hi - (double)lo + 1e-5);
+    }
+    const float* row = a.rows ? a.rows + (size_t)b * (2 * a.C + 1) : nullptr;
+    int box[IMAGE_MAX_ROIS][6];
+    for (int r = 0; r < a.R; ++r) {
+      const float* q = a.rois + ((size_t)b * a.R + r) * 4;
+      for (int j = 0; j < 4; ++j) box[r][j] = (int)std::fmin(std::fmax(q[j], -536870912.f), 536870912.f);
+      const int s0 = box[r][1] + w, e = box[r][3] - w + 1;
+      box[r][4] = s0 <= e ? s0 : e + 1; box[r][5] = s0 <= e ? e - 1 : s0;
+    }
+    for (int y = 0; y < a.H; ++y)
+      for (int x = 0; x < a.W; ++x) {
+        const size_t pix = (size_t)b * HW + (size_t)y * a.W + x;
+        uint8_t rgb[3] = {0, 0, 0};
+        if (a.source == SRC_FLOAT) {
+          const float* px = a.x.p + pix * a.x.cs;
+          for (int c = 0; c < 3; ++c) {
+            const int cc = a.C == 1 ? 0 : c;
+            float u = px[cc];
+            if (row) {
+              volatile float m = u * row[cc];
+              volatile float s1 = m + row[a.C + cc];
+              u = s1;
+              if (row[2 * a.C] != 0.f) u = std::fmin(std::fmax(u, 0.f), 1.f);
+            } else if (a.scale_each) {
+              volatile float s1 = std::fmin(std::fmax(u, lo), hi) + (-lo);
+              volatile float d = s1 / den;
+              u = d;
+            }
+            rgb[c] = to_byte(u);
+          }
+        } else {
+          int best = 0;
+          if (a.source == SRC_LABELS) {
+            best = a.labels[pix];
+          } else {
+            const float* px = a.x.p + pix * a.x.cs;
+            float m = px[0];
+            for (int c = 1; c < a.C; ++c) if (px[c] > m) { m = px[c]; best = c; }
+          }
+          if (best >= 0 && best < LABEL_PALETTE_SIZE) for (int c = 0; c < 3; ++c) rgb[c] = palette[best][c];
+        }
+        for (int r = 0; r < a.R; ++r) {
+          const int x0 = box[r][0], y0 = box[r][1], x1 = box[r][2], y1 = box[r][3];
+          const bool rows_hit = x >= x0 && x <= x1 && ((y >= y0 && y <= y0 + w - 1) || (y >= y1 - w + 1 && y <= y1));
+          const bool cols_hit = ((x >= x0 && x <= x0 + w - 1) || (x >= x1 - w + 1 && x <= x1)) && y >= box[r][4] && y <= box[r][5];
+          if (rows_hit || cols_hit) for (int c = 0; c < 3; ++c) rgb[c] = a.colours[r * 3 + c];
+        }
+        for (int c = 0; c < 3; ++c) a.out[pix * 3 + c] = rgb[c];
+      }
+  }
+}
+
 }  // namespace swn

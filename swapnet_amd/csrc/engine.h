@@ -443,6 +443,11 @@ class Model {
   virtual void get_output(int slot, float* dev_nchw) = 0;
   virtual TView output_view() = 0;              // NHWC view of self.fakes (logical channels: cloth_channels warp / 3 texture)
   virtual int output_channels() const = 0;
+  // NHWC view of a staged input, as the generator reads it, and its logical channels (the pipeline's image sheet): warp 0 bodys,
+  // 1 input_cloths; texture 0 input_textures, 2 cloths
+  virtual TView input_view(int slot, int* channels) = 0;
+  // texture models: the staged ROIs (B, num_roi, 4) = x0, y0, x1, y1 in image coordinates, device; NULL / 0 for any other model
+  virtual const float* staged_rois(int* num_roi) { *num_roi = 0; return nullptr; }
   virtual void forward(bool training, uint64_t seed) = 0;
   virtual void backward_D(float label_fake, float label_real) = 0;
   virtual void backward_G(float label_real) = 0;
@@ -564,8 +569,22 @@ class Pipeline {
   void run(bool use_graph);
   int32_t* labels() const { return labels_; }      // device (B, H, W): the hand-off label map of the last run
   bool graph_captured() const { return exec_ != nullptr; }
+  // The saved images of inference.py's loop body (get_current_visuals + save_images: unnormalize, scale_tensor(scale_each),
+  // decode_cloth_labels, draw_rois_on_texture, util.tensor2im) as the tail of the sequence -- seven launches of ops.h image_u8,
+  // recorded into the graph with the rest.  Allocates the sheet (IMAGE_SHEETS, B, H, W, 3), the min / max scratch and the small
+  // tables; drops a captured graph, so the next run is eager and captures again.  A second call replaces the tables.
+  static constexpr int IMAGE_SHEETS = 6;     // inputs_decoded, bodys_unnormalized, fakes_decoded, textures_unnormalized, fakes, fakes_scaled
+  void enable_images(const float body_mean[3], const float body_std[3], const float tex_mean[3], const float tex_std[3],
+                     const uint8_t* colours_host, int width, bool reference_quirk);
+  uint8_t* images() const { return sheet_; }       // device; NULL until enable_images
  private:
   void enqueue();
+  void enqueue_images();
+  uint8_t* sheet_ = nullptr;
+  float* minmax_ = nullptr;
+  float* rows_ = nullptr;          // [2][B][7]: the body table, then the texture table
+  uint8_t* colours_ = nullptr;     // (num_roi, 3)
+  int width_ = 1;
   Model& warp_;
   Model& tex_;
   int32_t* labels_ = nullptr;

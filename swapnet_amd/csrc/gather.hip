@@ -257,10 +257,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* src, int
   }
 }
 
-__constant__ uint8_t kPalette[19][3] = {
-    {0, 0, 0}, {128, 0, 0}, {255, 0, 0}, {0, 85, 0}, {255, 85, 0}, {0, 0, 85}, {0, 119, 221}, {85, 85, 0},
-    {0, 85, 85}, {85, 51, 0}, {52, 86, 128}, {0, 128, 0}, {0, 0, 255}, {51, 170, 221}, {0, 255, 255},
-    {85, 255, 170}, {170, 255, 85}, {255, 255, 0}, {255, 170, 0}};
+__constant__ uint8_t kPalette[LABEL_PALETTE_SIZE][3] = {SWN_LABEL_PALETTE};      // ops.h: shared with image_out.hip
 
 // MODE 0: palette decode -> uint8 NCHW rgb ; MODE 1: int32 labels
 template <int MODE>

@@ -340,6 +340,11 @@ class WarpModel final : public Model {
   }
   TView output_view() override { return Dx.batch(0, B).v.slice(0, Ccp); }
   int output_channels() const override { return Cc; }
+  TView input_view(int slot, int* channels) override {
+    if (slot == 0) { *channels = Cb; return body.v.slice(0, Cbp); }
+    if (slot == 1) { *channels = Cc; return cloth.v.slice(0, Ccp); }
+    throw Error(1, "input_view: unknown slot");
+  }
   // (the reverse-over-reverse pass of gp.cpp walks the n-layer PatchGAN through InstanceNorm; through BatchNorm and without a
   // norm layer in the device library only: batch_norm_bwd2 is a HIP kernel)
   bool supports_gradient_penalty() const override { return d_layers_ >= 1 && (d_norm_ == 0 || is_device_build()); }

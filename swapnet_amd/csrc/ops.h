@@ -1,7 +1,7 @@
 // swapnet_amd -- device op launchers.  The engine (engine.cpp) is written against this
 // header only.  The product implementation is the set of HIP translation units in this
 // directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, batch_norm.hip, losses.hip, optim.hip, gather.hip,
-// texture_batch.hip, warp_batch.hip, image_resize.hip).
+// texture_batch.hip, warp_batch.hip, image_resize.hip, image_out.hip).
 // tests/hostsim/hostsim_ops.cpp implements the same signatures with plain loops so that
 // the engine's graph / backward / packing logic can be checked in CI without a GPU; it is
 // never part of the shipped library.
@@ -560,6 +560,86 @@ inline void warp_batch_check(const WarpBatchArgs& a) {
   if (a.tgt_cloth.p && (!tileable(a.tgt_cloth) || a.tgt_cloth.C != t.C || !same(a.tgt_cloth))) throw Error(1, "warp_batch tgt_cloth: view mismatch");
   for (int k = 0; k < a.nbody; ++k)
     if (!tileable(a.body_out[k]) || a.body_out[k].C != 4 || !same(a.body_out[k])) throw Error(1, "warp_batch body: view mismatch");
+}
+
+// ---- saved-image visuals (image_out.hip) ------------------------------------------------------------------------------------------
+// What inference.py does per image between a model's tensors and Image.fromarray -- unnormalize / scale_tensor(scale_each)
+// (datasets/data_utils.py:41-90), decode_cloth_labels (util/decode_labels.py:24-55), draw_rois_on_texture (util/draw_rois.py:16-47)
+// and util.tensor2im (util/util.py:9-32) -- for a whole batch: one NHWC view (or one label map) in, (B,H,W,3) interleaved bytes out.
+//
+// The 19 colours of util/decode_labels.py:8-21, one definition for every unit that holds them (gather.hip's decode_labels, image_out.hip
+// and the host form in engine.cpp)
+#define SWN_LABEL_PALETTE                                                                                                             \
+  {0, 0, 0}, {128, 0, 0}, {255, 0, 0}, {0, 85, 0}, {255, 85, 0}, {0, 0, 85}, {0, 119, 221}, {85, 85, 0}, {0, 85, 85}, {85, 51, 0},    \
+  {52, 86, 128}, {0, 128, 0}, {0, 0, 255}, {51, 170, 221}, {0, 255, 255}, {85, 255, 170}, {170, 255, 85}, {255, 255, 0}, {255, 170, 0}
+constexpr int LABEL_PALETTE_SIZE = 19;
+// Sources (one per call):
+//   SRC_FLOAT   x has C = 3 logical channels, or C = 1 replicated to three (tensor2im's grayscale branch);
+//   SRC_ARGMAX  x has C = number of labels; the first maximum over the channels selects a colour (argmax, then the palette);
+//   SRC_LABELS  an int32 (B,H,W) map selects the colour.
+// Palette sources write the palette's bytes; a label outside [0, 19) gives black.  (The reference passes decode_cloth_labels' uint8
+// tensor through tensor2im's float formula, (x + 1) / 2 * 255 cast to uint8, which wraps modulo 256 -- numpy leaves that cast
+// undefined, it is not reproducible and not reproduced.)
+// Float sources, per element v of image b and channel c, every step ONE correctly rounded fp32 operation:
+//   rows != NULL:  u = v * rows[b][c] + rows[b][C + c] (a product, then a sum: never fused); rows[b][2C] != 0: u = min(max(u, 0), 1)
+//   scale_each:    lo / hi = min / max over the C LOGICAL channels of image b (pad channels of the view take no part);
+//                  den = (float)((double)hi - (double)lo + 1e-5);  u = (min(max(v, lo), hi) + (-lo)) / den       (scale_tensor)
+//   neither:       u = v                                                      (rows and scale_each together are refused)
+//   RANGE_SIGNED:  byte = (u + 1) / 2 * 255       (tensor2im: also what the reference applies to its [0,1] visuals, whose saved
+//   RANGE_UNIT:    byte = u * 255                  images therefore span 127..255)
+// both saturated to [0, 255] and truncated: equal to numpy's astype(uint8) wherever that is defined ([0, 256)), the saturating value
+// elsewhere.  A NaN anywhere in a float source leaves that pixel's bytes -- under scale_each the whole image's -- unspecified.
+// The min / max reduction stays on the device: chunks = image_u8_chunks(H, W) <= 64 blocks per image leave wave-reduced partials in
+// minmax[b][chunk][2] (caller's scratch, nothing of it needs initialising), the conversion kernel's waves finish it.  No atomics,
+// no host read: capturable, and exact because min and max do not depend on the order.
+// ROI outlines (R > 0), drawn over the converted bytes in the same pass: rois (B,R,4) = x0, y0, x1, y1, colours (R,3) bytes, both
+// device arrays, width >= 1.  A pixel takes the colour of the LAST ROI whose outline covers it, as Pillow's sequential
+// ImageDraw.rectangle(box, outline = colour, width = width) calls leave it (Draw.c ImagingDrawRectangle): coordinates truncate toward
+// zero; rows y0 .. y0 + width - 1 and y1 - width + 1 .. y1 over columns x0 .. x1; columns x0 .. x0 + width - 1 and x1 - width + 1 .. x1
+// over the rows from a = y0 + width towards e = y1 - width + 1, e itself excluded (a .. e - 1, or e + 1 .. a where a > e: a box flatter
+// than twice the width paints below itself, the all-zero box with width 1 paints (0,0) and (0,1)); everything clipped to the image.
+// x1 < x0 or y1 < y0 is Pillow's ValueError: the callers refuse such boxes before anything is launched.
+enum ImageSource : int { SRC_FLOAT = 0, SRC_ARGMAX = 1, SRC_LABELS = 2 };
+enum ImageRange : int { RANGE_SIGNED = 0, RANGE_UNIT = 1 };
+constexpr int IMAGE_MAX_ROIS = 16, IMAGE_MAX_CHUNKS = 64;
+struct ImageU8Args {
+  int source = SRC_FLOAT;
+  TView x; int C = 0;                                        // SRC_FLOAT / SRC_ARGMAX: the view and its logical channels
+  const int32_t* labels = nullptr; int B = 0, H = 0, W = 0;  // SRC_LABELS: (B,H,W); the other sources take B, H, W from x
+  const float* rows = nullptr;                               // device [B][2C + 1]: scale[C], shift[C], clamp flag
+  int scale_each = 0; float* minmax = nullptr;               // device scratch [B][image_u8_chunks(H, W)][2]
+  int range = RANGE_SIGNED;
+  const float* rois = nullptr; int R = 0; const uint8_t* colours = nullptr; int width = 1;
+  uint8_t* out = nullptr;                                    // (B,H,W,3)
+};
+inline int image_u8_chunks(int H, int W) {                   // 1024 pixels per block, at most one wave's worth of partials
+  const size_t c = ((size_t)H * W + 1023) / 1024;
+  return (int)(c < 1 ? 1 : (c > (size_t)IMAGE_MAX_CHUNKS ? IMAGE_MAX_CHUNKS : c));
+}
+void image_u8(Stream& s, const ImageU8Args& a);
+// the argument checks of every image_u8 implementation (the HIP launcher and the host loop of engine.cpp); fills B, H, W from the view
+inline ImageU8Args image_u8_check(ImageU8Args a) {
+  if (!a.out) throw Error(1, "image_u8: NULL output");
+  if (a.source == SRC_LABELS) {
+    if (!a.labels) throw Error(1, "image_u8: SRC_LABELS without a label map");
+  } else if (a.source == SRC_FLOAT || a.source == SRC_ARGMAX) {
+    if (!a.x.p || a.x.cs < a.C) throw Error(1, "image_u8: empty view, or logical channels beyond the pixel stride");
+    a.B = a.x.N; a.H = a.x.H; a.W = a.x.W;
+    if (a.source == SRC_FLOAT && a.C != 3 && a.C != 1) throw Error(1, "image_u8: a float source has 3 channels, or 1 (grayscale), got " + std::to_string(a.C));
+    if (a.source == SRC_ARGMAX && (a.C < 1 || a.C > 256)) throw Error(1, "image_u8: SRC_ARGMAX takes 1 to 256 label channels");
+  } else {
+    throw Error(1, "image_u8: source [" + std::to_string(a.source) + "] is not recognized (0 float, 1 argmax, 2 labels)");
+  }
+  if (a.B < 1 || a.H < 1 || a.W < 1) throw Error(1, "image_u8: empty sizes");
+  if ((size_t)a.H * a.W > (size_t)1 << 28) throw Error(1, "image_u8: images of more than 2^28 pixels are not implemented");
+  if (a.range != RANGE_SIGNED && a.range != RANGE_UNIT) throw Error(1, "image_u8: range [" + std::to_string(a.range) + "] is not recognized (0 signed, 1 unit)");
+  if (a.source != SRC_FLOAT && (a.rows || a.scale_each)) throw Error(1, "image_u8: the affine table and scale_each apply to float sources only");
+  if (a.rows && a.scale_each) throw Error(1, "image_u8: the affine table and scale_each exclude each other");
+  if (a.scale_each && !a.minmax) throw Error(1, "image_u8: scale_each needs the min/max scratch");
+  if (a.R < 0 || a.R > IMAGE_MAX_ROIS) throw Error(1, "image_u8: 0 to " + std::to_string(IMAGE_MAX_ROIS) + " ROIs per image, got " + std::to_string(a.R));
+  if (a.R > 0 && (!a.rois || !a.colours)) throw Error(1, "image_u8: ROI outlines need the ROI table and the colour table");
+  if (a.R > 0 && (a.width < 1 || a.width > (1 << 20))) throw Error(1, "image_u8: outline width in [1, 2^20]");
+  return a;
 }
 
 // ---- losses: each writes the plain MEAN loss into *loss_out (device float) and, if a grad

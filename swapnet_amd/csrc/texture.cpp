@@ -443,6 +443,12 @@ class TextureModel final : public Model {
   }
   TView output_view() override { return Dx.batch(0, B).v.slice(0, 4); }
   int output_channels() const override { return 3; }
+  TView input_view(int slot, int* channels) override {
+    if (slot == 0) { *channels = 3; return tex.v; }
+    if (slot == 2) { *channels = Cc; return Dx.batch(0, B).v.slice(4, Ccp); }
+    throw Error(1, "input_view: unknown slot");
+  }
+  const float* staged_rois(int* n) override { *n = num_roi; return rois; }
   void forward(bool training, uint64_t seed) override {        // texture_model.py:121-125
     G->training = training; G->seed = seed;
     G->bn_training = training;         // (BatchNorm sites -- unet_128's, the TextureModule's under --norm batch: nn.Module.train() / eval())

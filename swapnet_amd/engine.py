@@ -168,6 +168,7 @@ class NativeModel:
             raise NotImplementedError("normalization layer [%s] is not found" % norm)
         self.norm = norm
         self.share = share
+        self.num_roi = share.num_roi if share is not None else int(num_roi)
         if share is not None:
             if share.kind != kind:
                 raise ValueError("a sharing model must be of its sharer's kind")
@@ -722,6 +723,88 @@ def op_resize_u8(ctx, images, hs, ws):
     return op_resize_u8_packed(ctx, *pack_u8_images(images), hs, ws)
 
 
+SRC_FLOAT, SRC_ARGMAX, SRC_LABELS = 0, 1, 2          # ops.h ImageSource
+RANGE_SIGNED, RANGE_UNIT = 0, 1                      # ops.h ImageRange
+IMAGE_NAMES = ("inputs_decoded", "bodys_unnormalized", "fakes_decoded", "textures_unnormalized", "fakes", "fakes_scaled")
+
+
+def image_rows(batch, channels, mean, std, reference_quirk=True):
+    """The (B, 2C + 1) float32 table of swn_op_image_u8 -- scale[C], shift[C], clamp flag per image -- that restates
+    util.unnormalize(tensor, mean, std): under `reference_quirk` its zip over dim 0 (datasets/data_utils.py:41-58: image b < len(mean)
+    gets (std[b], mean[b]) on all its channels and is clamped, the images behind it stay as they are, unclamped), otherwise the
+    per-channel form for every image."""
+    rows = torch.zeros((batch, 2 * channels + 1), dtype=torch.float32)
+    rows[:, :channels] = 1.0
+    if reference_quirk:
+        for b, (m, s) in enumerate(zip(mean, std)):
+            if b >= batch:
+                break
+            rows[b, :channels], rows[b, channels:2 * channels], rows[b, 2 * channels] = float(s), float(m), 1.0
+    else:
+        if len(mean) != channels or len(std) != channels:
+            raise ValueError("image_rows: %d channels, but %d means and %d stds" % (channels, len(mean), len(std)))
+        rows[:, :channels] = torch.tensor([float(s) for s in std], dtype=torch.float32)
+        rows[:, channels:2 * channels] = torch.tensor([float(m) for m in mean], dtype=torch.float32)
+        rows[:, 2 * channels] = 1.0
+    return rows
+
+
+def check_roi_boxes(rois):
+    """Pillow's own refusal (ImageDraw.rectangle), raised before the library is called: a box is x0, y0, x1, y1 with x1 >= x0, y1 >= y0."""
+    r = torch.as_tensor(rois).detach().to(device="cpu", dtype=torch.float32)
+    if r.dim() != 3 or r.shape[2] != 4:
+        raise ValueError("ROIs must be (B, R, 4) rows x0, y0, x1, y1, got %s" % (tuple(r.shape),))
+    if not bool(torch.isfinite(r).all()):
+        raise ValueError("ROI coordinates must be finite")
+    if bool((r[..., 2] < r[..., 0]).any()):
+        raise ValueError("x1 must be greater than or equal to x0")
+    if bool((r[..., 3] < r[..., 1]).any()):
+        raise ValueError("y1 must be greater than or equal to y0")
+    return r
+
+
+def op_image_u8(ctx, x=None, labels=None, source=None, rows=None, scale_each=False, range=RANGE_SIGNED, rois=None, colours=None, width=1):
+    """swn_op_image_u8: util.tensor2im for a whole batch on the device, with unnormalize (`rows`, see image_rows), scale_tensor(
+    scale_each=True), decode_cloth_labels (argmax or label source) and draw_rois_on_texture (`rois` (B,R,4), `colours` (R,3) uint8,
+    `width`) folded in.  x (B,C,H,W) float, or labels (B,H,W) int -> (B,H,W,3) uint8 on the context's device."""
+    if (x is None) == (labels is None):
+        raise ValueError("image_u8: exactly one of x (B,C,H,W) and labels (B,H,W)")
+    if source is None:
+        source = SRC_LABELS if x is None else SRC_FLOAT
+    if (source == SRC_LABELS) != (x is None):
+        raise ValueError("image_u8: labels go with SRC_LABELS, x with the float and argmax sources")
+    xd = lab = rd = roid = cold = None
+    if x is not None:
+        xd = _dev(ctx, x)
+        if xd.dim() != 4:
+            raise ValueError("image_u8: x must be (B,C,H,W), got %s" % (tuple(xd.shape),))
+        b, c, h, w = xd.shape
+    else:
+        lab = _dev(ctx, labels, torch.int32)
+        if lab.dim() != 3:
+            raise ValueError("image_u8: labels must be (B,H,W), got %s" % (tuple(lab.shape),))
+        (b, h, w), c = lab.shape, 0
+    if rows is not None:
+        rd = _dev(ctx, torch.as_tensor(rows))
+        if tuple(rd.shape) != (b, 2 * c + 1):
+            raise ValueError("image_u8: rows must be (B, 2C + 1) = %s, got %s" % ((b, 2 * c + 1), tuple(rd.shape)))
+    r = 0
+    if rois is not None:
+        roid = check_roi_boxes(rois).to(ctx.device).contiguous()
+        r = roid.shape[1]
+        if roid.shape[0] != b:
+            raise ValueError("image_u8: ROIs for %d images, batch of %d" % (roid.shape[0], b))
+        cold = _dev(ctx, torch.as_tensor(colours), torch.uint8)
+        if tuple(cold.shape) != (r, 3):
+            raise ValueError("image_u8: colours must be (R, 3) = %s, got %s" % ((r, 3), tuple(cold.shape)))
+    out = torch.empty((b, h, w, 3), dtype=torch.uint8, device=ctx.device)
+    if ctx.owns_stream:                     # (the uploads above ran on torch's stream)
+        torch.cuda.current_stream(ctx.device).synchronize()
+    ctx.lib.call("swn_op_image_u8", ctx.handle, _C.ptr(xd), b, c, h, w, _C.ptr(lab), int(source), _C.ptr(rd), int(bool(scale_each)),
+                 int(range), _C.ptr(roid), r, _C.ptr(cold), int(width), _C.ptr(out))
+    return out
+
+
 AMAX_SLOT = 256                     # floats of one amax slot (ops.h)
 EW_ACT_FWD, EW_ACT_BWD, EW_AXPY = 0, 1, 2
 RS_UPSAMPLE_FWD, RS_UPSAMPLE_BWD, RS_MAXPOOL_FWD, RS_MAXPOOL_BWD, RS_REFLECT_FOLD, RS_ACT_PATTERN = 0, 1, 2, 3, 4, 5
@@ -1000,6 +1083,29 @@ class NativePipeline:
         n = self.warp.B * self.warp.H * self.warp.W
         self.ctx.sync()
         return _wrap_pointer(p.value, n, self.ctx.device, "<i4").reshape(self.warp.B, self.warp.H, self.warp.W).clone()
+
+    def enable_images(self, body_norm_stats, texture_norm_stats, colours, width, reference_quirk=True):
+        """swn_pipeline_enable_images: from the next run on the sequence ends with the image launches (inside the captured graph);
+        *_norm_stats = (mean3, std3) as the reference's options hold them, colours (num_roi, 3) uint8, width in pixels."""
+        import numpy as np
+        col = np.ascontiguousarray(np.asarray(colours, dtype=np.uint8))
+        if col.shape != (self.texture.num_roi, 3):
+            raise ValueError("enable_images: colours must be (num_roi, 3) = %s, got %s" % ((self.texture.num_roi, 3), col.shape))
+        f3 = lambda v: (C.c_float * 3)(*[float(t) for t in v])
+        (bm, bs), (tm, ts) = body_norm_stats, texture_norm_stats
+        self.lib.call("swn_pipeline_enable_images", self.handle, f3(bm), f3(bs), f3(tm), f3(ts),
+                      col.ctypes.data_as(C.POINTER(C.c_uint8)), int(width), int(bool(reference_quirk)))
+
+    def images(self):
+        """The image sheet of the last run in ONE device-to-host copy: name -> (B,H,W,3) uint8 numpy array (IMAGE_NAMES order)."""
+        p, k = C.c_void_p(), C.c_int()
+        self.lib.call("swn_pipeline_images", self.handle, C.byref(p), C.byref(k))
+        B, H, W = self.warp.B, self.warp.H, self.warp.W
+        self.ctx.sync()
+        sheet = _wrap_pointer(p.value, k.value * B * H * W * 3, self.ctx.device, "|u1").cpu().numpy().reshape(k.value, B, H, W, 3)
+        if self.ctx.device.type != "cuda":
+            sheet = sheet.copy()
+        return OrderedDict(zip(IMAGE_NAMES, sheet))
 
     def close(self):
         if getattr(self, "handle", None):

@@ -94,6 +94,26 @@ class BaseModel(ABC):
     def get_current_visuals(self):
         return OrderedDict(self._attrs("", self.visual_names))
 
+    def get_current_images(self):
+        """What util.visualizer.save_images would write for get_current_visuals() (util/util.py:9-32 tensor2im per visual), for ALL
+        images of the batch, computed on the device from the tensors already there (engine.op_image_u8): name -> (B,H,W,3) uint8
+        numpy array.  compute_visuals() / get_current_visuals() are neither called nor changed by it."""
+        from .. import engine
+        ctx = self.backend.ctx
+        return OrderedDict((name, engine.op_image_u8(ctx, **spec).cpu().numpy()) for name, spec in self._image_specs())
+
+    def _image_specs(self):
+        """(visual name, keyword arguments of engine.op_image_u8) in visual_names order."""
+        return []
+
+    @staticmethod
+    def _label_image_spec(t):
+        """A cloth segmentation as the models hold it: the integer label map (B,H,W), or its one-hot / logit form (B,C,H,W)."""
+        from .. import engine
+        if t.dim() == 3:
+            return dict(labels=t, source=engine.SRC_LABELS)
+        return dict(x=t, source=engine.SRC_ARGMAX)
+
     def get_current_losses(self):
         """One small D2H copy + sync per call (base_model.py:139-147 does float(loss) per name)."""
         self._fetch_losses()

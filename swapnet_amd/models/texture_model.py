@@ -97,12 +97,33 @@ class TextureModel(BaseGAN):
 
     def compute_visuals(self):
         self.textures_unnormalized = unnormalize(self.textures.cpu(), *self.opt.texture_norm_stats)
-        # util/draw_rois (ROI rectangle overlay, display only) is out of scope
+        # (no ROI overlay on this host tensor; get_current_images() draws util/draw_rois' outlines on the device)
         cl = labels_to_onehot(self.cloths, self.opt.cloth_channels, ctx=self.backend.ctx) if self.cloths.dim() == 3 else self.cloths
         self.cloths_decoded = decode_cloth_labels(cl, ctx=self.backend.ctx)
         self.fakes_scaled = scale_tensor(self.fakes.cpu(), scale_each=True)
         if self.is_train:
             self.targets_unnormalized = unnormalize(self.targets.cpu(), *self.opt.texture_norm_stats)
+
+    def _image_specs(self):
+        """The reference's five visuals (texture_model.py:75-89), textures_unnormalized WITH the ROI outlines of util/draw_rois.py that
+        compute_visuals() leaves out."""
+        from ..engine import image_rows
+        from ..util.draw_rois import BODY_COLORS
+        B, _, _, W = self.textures.shape
+        rows = image_rows(B, 3, *self.opt.texture_norm_stats)
+        tex = dict(x=self.textures, rows=rows)
+        width = int(round(0.01 * W))
+        if width:                                   # (Pillow draws nothing at width 0)
+            rois = self.rois
+            if getattr(self, "_compact", None) is not None:       # a compact batch holds the RAW table: the staged one, in image coordinates
+                from ..datasets.gpu_texture_batch import expand_batch
+                rois = expand_batch(self.backend.ctx, self._compact, self.opt.cloth_channels)["rois"]
+            tex.update(rois=rois, colours=BODY_COLORS[:rois.shape[1]], width=width)
+        specs = [("textures_unnormalized", tex), ("cloths_decoded", self._label_image_spec(self.cloths)),
+                 ("fakes", dict(x=self.fakes)), ("fakes_scaled", dict(x=self.fakes, scale_each=True))]
+        if self.is_train:
+            specs.append(("targets_unnormalized", dict(x=self.targets, rows=rows)))
+        return specs
 
     def get_D_inchannels(self):
         return self.opt.texture_channels + self.opt.cloth_channels

@@ -43,6 +43,16 @@ class WarpModel(BaseGAN):
             self.targets_decoded = decode_cloth_labels(as_onehot(self.targets), ctx=self.backend.ctx)
         self.fakes_decoded = decode_cloth_labels(self.fakes, ctx=self.backend.ctx)
 
+    def _image_specs(self):
+        from ..engine import image_rows
+        B = self.bodys.shape[0]
+        specs = [("inputs_decoded", self._label_image_spec(self.inputs)),
+                 ("bodys_unnormalized", dict(x=self.bodys, rows=image_rows(B, self.bodys.shape[1], *self.opt.body_norm_stats))),
+                 ("fakes_decoded", self._label_image_spec(self.fakes))]
+        if self.is_train:
+            specs.append(("targets_decoded", self._label_image_spec(self.targets)))
+        return specs
+
     def define_G(self):
         return WarpModule(body_channels=self.body_channels, cloth_channels=self.cloth_channels, backend=self.backend)
 

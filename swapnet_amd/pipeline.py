@@ -16,9 +16,19 @@ from .modules.native import NativeBackend
 
 
 class TwoStagePipeline:
-    def __init__(self, warp_state_dict, texture_state_dict, img_size=128, num_roi=12, ctx=None, lib=None, use_graph=True):
+    def __init__(self, warp_state_dict, texture_state_dict, img_size=128, num_roi=12, ctx=None, lib=None, use_graph=True, images=None):
+        """images = dict(body_norm_stats=(mean3, std3), texture_norm_stats=(mean3, std3)[, colours=(num_roi,3) uint8, width_factor=0.01,
+        reference_quirk=True]) arms the image sheet: every call then also leaves the six images inference.py would save, as uint8 on the
+        device inside the same graph; `images()` fetches them."""
         self.ctx = ctx or engine.default_context(lib=lib)
         self.use_graph = use_graph
+        self.image_options = dict(images) if images is not None else None
+        if self.image_options is not None:
+            missing = {"body_norm_stats", "texture_norm_stats"} - set(self.image_options)
+            unknown = set(self.image_options) - {"body_norm_stats", "texture_norm_stats", "colours", "width_factor", "reference_quirk"}
+            if missing or unknown:
+                raise ValueError("images: missing %s, unknown %s" % (sorted(missing), sorted(unknown)))
+        self._last = None
         self.warp = NativeBackend("warp", is_train=False, ctx=self.ctx)
         self.texture = NativeBackend("texture", is_train=False, num_roi=num_roi, ctx=self.ctx,
                                      default_shape=(1, img_size, img_size))
@@ -32,7 +42,26 @@ class TwoStagePipeline:
         key = (B, H, W)
         if key not in self._pipes:
             self._pipes[key] = engine.NativePipeline(w, t)
+            if self.image_options is not None:
+                from .util.draw_rois import BODY_COLORS
+                o = self.image_options
+                colours = o["colours"] if o.get("colours") is not None else BODY_COLORS[:t.num_roi]
+                width = max(1, int(round(o.get("width_factor", 0.01) * W)))
+                self._pipes[key].enable_images(o["body_norm_stats"], o["texture_norm_stats"], colours, width, o.get("reference_quirk", True))
         return w, t, self._pipes[key]
+
+    def images(self):
+        """The images of the last call, name -> (B,H,W,3) uint8 numpy array, under the reference's visual names (warp_model.py:60,
+        texture_model.py:58-63): inputs_decoded, bodys_unnormalized, fakes_decoded, textures_unnormalized (ROI outlines drawn),
+        cloths_decoded (the same array as fakes_decoded: the texture stage's cloth input IS the warped label map), fakes,
+        fakes_scaled.  One device-to-host copy."""
+        if self.image_options is None:
+            raise ValueError("images(): the pipeline was built without images=dict(body_norm_stats=..., texture_norm_stats=...)")
+        if self._last is None:
+            raise ValueError("images(): call the pipeline first")
+        out = self._last.images()
+        out["cloths_decoded"] = out["fakes_decoded"]
+        return out
 
     @torch.no_grad()
     def __call__(self, bodys, input_cloths, textures, rois, return_labels=False):
@@ -48,7 +77,10 @@ class TwoStagePipeline:
         else:
             w.set_input(1, input_cloths)
         t.set_input(0, textures)
+        if self.image_options is not None:
+            engine.check_roi_boxes(rois)                # Pillow's ValueError for a reversed box, before anything is launched
         t.set_input(1, rois)
+        self._last = pipe
         self.last_call_was_graph_replay = pipe.run(self.use_graph)
         out = t.output()
         return (out, pipe.labels()) if return_labels else out
