@@ -41,7 +41,8 @@ typedef struct swn_model swn_model;
 int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lambda_gp; 4: swn_route_*, swn_model_step_captured, swn_model_create_shared;
                                 5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit; 8: swn_op_loss, swn_op_bias_grad;
                                 9: swn_op_norm_act, swn_op_elementwise, swn_op_resample (additions since, version unchanged: swn_op_resize_u8,
-                                swn_model_set_input_texture_sources, swn_op_conv_views) */
+                                swn_model_set_input_texture_sources, swn_op_conv_views, swn_op_chain_resample, swn_op_warp_batch_ex,
+                                swn_model_set_input_warp_batch_ex) */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -244,6 +245,14 @@ int swn_model_set_input_texture_sources(swn_model* m, const uint8_t* src, size_t
 int swn_model_set_input_warp_batch(swn_model* m, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels,
                                    const uint8_t* tgt_labels, int hl, int wl, const double* maps, int nmaps, const float* mean3,
                                    const float* std3, int load_size, int x_min, int y_min);
+/* The same with a trailing `flags`.  Bit 0: the map table may hold kind 3, RandomPerspective resampled BICUBIC as torchvision 0.4.0
+ * resamples it (datasets/__init__.py:87-110 get_transforms -> transforms.RandomPerspective, applied per channel by
+ * datasets/data_utils.py:346-361; swn_op_chain_resample below has the rule) -- the input cloth is then a float map that need not be
+ * 0 or 1, and its amax slot is measured after the launch like any other's.  flags 0 is swn_model_set_input_warp_batch itself: the
+ * same launch, the same bytes.  PRECONDITION: at most one kind-3 row per chain; kind 3 only with bit 0 set.  Other bits: refused. */
+int swn_model_set_input_warp_batch_ex(swn_model* m, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels,
+                                      const uint8_t* tgt_labels, int hl, int wl, const double* maps, int nmaps, const float* mean3,
+                                      const float* std3, int load_size, int x_min, int y_min, int flags);
 /* slot 0: self.fakes (B,19,H,W) warp / (B,3,H,W) texture */
 int swn_model_get_output(swn_model* m, int slot, float* dev_nchw);
 /* named intermediate activation (debug / per-level parity tests), copied out as NCHW.  Warp models, net 0, also name the buffers
@@ -496,6 +505,26 @@ int swn_op_norm_act_time(swn_ctx* ctx, int kind, int what, const float* x, const
  * NEAREST sampling.  swapnet_amd/datasets/gpu_augment.py draws the parameters like torchvision's transforms do. */
 int swn_op_affine_gather(swn_ctx* ctx, const float* src, float* dst, int b, int c, int h, int w, const double* maps,
                          int nmaps);
+/* swn_op_affine_gather with one more kind in the table: kind 3 = perspective resampled BICUBIC, c0..c7 as for kind 2 -- what
+ * torchvision 0.4.0's RandomPerspective (datasets/__init__.py:87-110 get_transforms; per channel through
+ * datasets/data_utils.py:346-361 per_channel_transform, whose Image.fromarray of a float32 array is a mode-"F" image) computes:
+ * img.transform(size, PERSPECTIVE, coeffs, Image.BICUBIC).  Bit-identical to Pillow given the same coefficients.  In IEEE double, one
+ * rounded operation per step, no fused multiply-add, for output pixel (x, y) of the h x w image:
+ *   xc = x + .5, yc = y + .5;  den = c6 xc + c7 yc + 1;  fx = (c0 xc + c1 yc + c2) / den;  fy = (c3 xc + c4 yc + c5) / den
+ *   FLOOR(v) = (int)floor(v) for v < 0, else (int)v;  FLOOR(fx) outside [0, w) or FLOOR(fy) outside [0, h): the output is 0 (the fill)
+ *   fx -= .5, fy -= .5;  x0 = FLOOR(fx), y0 = FLOOR(fy);  dx = fx - x0, dy = fy - y0;  the 4 x 4 window starts at (x0 - 1, y0 - 1), its
+ *   column indices each clipped to [0, w - 1]
+ *   cub(v1, v2, v3, v4, d) = p1 + d (p2 + d (p3 + d p4)),  p1 = v2,  p2 = -v1 + v3,  p3 = 2 (v1 - v2) + v3 - v4,  p4 = -v1 + v2 - v3 + v4
+ *   window row 0 uses its row index clipped to [0, h - 1]; rows 1 to 3 are evaluated only where their index is inside the image, an
+ *   outside row takes the previous row's value;  row value = cub(four texels, dx) with p2, p3, p4 evaluated in FP32 on the fp32 texels
+ *   (Pillow's macro receives the FLOAT32 lvalues) and p1 and the Horner form in double;  pixel = (float)cub(r0, r1, r2, r3, dy) in double
+ * Kinds 0 to 2 keep their NEAREST meaning.  The rows behind the kind-3 row are walked first from the output pixel; the rows in front of
+ * it define the image the sixteen taps read: each tap walks them backwards like swn_op_affine_gather, and a tap that leaves the image
+ * on the way reads 0.  PRECONDITION: at most one kind-3 row per chain (one RandomOrder draw cannot produce more; a further one is
+ * resampled NEAREST, nothing is accessed out of bounds); coefficients finite with |fx|, |fy| < 2^31; h * w < 2^31.  A table without
+ * kind 3 gives swn_op_affine_gather's bytes.  What stays unpinned is torchvision's float32 least-squares fit of the coefficients. */
+int swn_op_chain_resample(swn_ctx* ctx, const float* src, float* dst, int b, int c, int h, int w, const double* maps,
+                          int nmaps);
 /* TextureDataset.__getitem__ (datasets/texture_dataset.py:87-160, datasets/data_utils.py:169-295) for a whole batch as ONE device
  * launch, from the compact form (arguments as swn_model_set_input_texture_batch; h x w = the crop window at (x_min, y_min)).
  * With (y, x) a pixel of the window, everything in fp32, one correctly rounded operation per step:
@@ -549,10 +578,21 @@ int swn_op_resize_u8(swn_ctx* ctx, const uint8_t* src, size_t src_bytes, const i
  *                           v = h0 * (w0 * t[y0,x0] + w1 * t[y0,x1]) + h1 * (w0 * t[y1,x0] + w1 * t[y1,x1])
  *                                                       ToTensor, Normalize, F.interpolate(size = Ls, mode = "bilinear"), crop
  * The float one-hot map of the host chain is never built.  target_cloths_nchw may be NULL (then tgt_labels may be too).  As with
- * swn_op_affine_gather, RandomPerspective is resampled NEAREST (the reference: BICUBIC); everything else is bit-identical. */
+ * swn_op_affine_gather, a kind-2 RandomPerspective is resampled NEAREST (the reference: BICUBIC, which swn_op_warp_batch_ex offers);
+ * everything else is bit-identical. */
 int swn_op_warp_batch(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int hl,
                       int wl, const double* maps, int nmaps, const float* mean3, const float* std3, int load_size, int x_min, int y_min,
                       int h, int w, int cloth_channels, float* bodys_nchw, float* input_cloths_nchw, float* target_cloths_nchw);
+/* The same with a trailing `flags`.  Bit 0: the table may hold kind 3 (swn_op_chain_resample: RandomPerspective resampled BICUBIC,
+ * datasets/__init__.py:87-110, datasets/data_utils.py:346-361).  Channel c of input_cloths_nchw is then c's chain evaluated by that
+ * rule at (near(sy, hl), near(sx, wl)) of the hl x wl map whose texels are the indicators in_labels == c (0 for c = 0): the reference's
+ * one-hot map -> per-channel PIL chain -> F.interpolate nearest -> crop, bit for bit given the same coefficients.  bodys_nchw and
+ * target_cloths_nchw do not depend on the flag.  flags 0 is swn_op_warp_batch itself: the same launch, the same bytes.
+ * PRECONDITION: at most one kind-3 row per chain; kind 3 only with bit 0 set.  Other bits: refused. */
+int swn_op_warp_batch_ex(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int hl,
+                         int wl, const double* maps, int nmaps, const float* mean3, const float* std3, int load_size, int x_min, int y_min,
+                         int h, int w, int cloth_channels, float* bodys_nchw, float* input_cloths_nchw, float* target_cloths_nchw,
+                         int flags);
 /* GANLoss(gan_mode)(prediction, target_is_real) (modules/loss.py:110-130) with the target scalar already drawn
  * (`label`; the smooth-label draw stays host-side like in the reference, loss.py:65-108): mean BCE-with-logits /
  * MSE / +-mean over ALL elements of pred (N,C,H,W).  loss_out = device float; dpred (optional, same shape) receives

@@ -67,6 +67,7 @@ _PROTOS = {
     "swn_model_set_input_texture_sources": ([_vp, _vp, C.c_size_t, _vp, _i, _i, _i, _vp, _i, _i, _fp, _i, _fp, C.POINTER(_f), C.POINTER(_f),
                                              _i, _i], _i),
     "swn_model_set_input_warp_batch": ([_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, C.POINTER(_f), C.POINTER(_f), _i, _i, _i], _i),
+    "swn_model_set_input_warp_batch_ex": ([_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i], _i),
     "swn_model_get_output": ([_vp, _i, _fp], _i),
     "swn_model_get_tap": ([_vp, _i, C.c_char_p, _fp, C.POINTER(_i * 4)], _i),
     "swn_model_get_tap_grad": ([_vp, _i, C.c_char_p, _fp, C.POINTER(_i * 4)], _i),
@@ -124,6 +125,9 @@ _PROTOS = {
     "swn_op_resize_u8": ([_vp, _vp, C.c_size_t, _vp, _i, _i, _i, _vp], _i),
     "swn_op_warp_batch": ([_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i, _i,
                           _fp, _fp, _fp], _i),
+    "swn_op_warp_batch_ex": ([_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i, _i,
+                             _fp, _fp, _fp, _i], _i),
+    "swn_op_chain_resample": ([_vp, _fp, _fp, _i, _i, _i, _i, _vp, _i], _i),
     "swn_op_gan_loss": ([_vp, _i, _fp, _i, _i, _i, _i, _f, _i, _f, _fp, _fp], _i),
     "swn_op_loss": ([_vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _fp, _fp, _fp], _i),
     "swn_op_bias_grad": ([_vp, _fp, _i, _i, _i, _i, _i, _fp], _i),

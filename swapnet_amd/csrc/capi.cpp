@@ -393,9 +393,15 @@ int swn_model_set_input_texture_sources(swn_model* m, const uint8_t* src, size_t
 int swn_model_set_input_warp_batch(swn_model* m, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels,
                                    const uint8_t* tgt_labels, int hl, int wl, const double* maps, int nmaps, const float* mean3,
                                    const float* std3, int load_size, int x_min, int y_min) {
+  return swn_model_set_input_warp_batch_ex(m, body, b, hb, wb, in_labels, tgt_labels, hl, wl, maps, nmaps, mean3, std3, load_size, x_min, y_min, 0);
+}
+int swn_model_set_input_warp_batch_ex(swn_model* m, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels,
+                                      const uint8_t* tgt_labels, int hl, int wl, const double* maps, int nmaps, const float* mean3,
+                                      const float* std3, int load_size, int x_min, int y_min, int flags) {
   return guard([&] {
     REQUIRE(m && body && in_labels && mean3 && std3, "NULL argument");
-    m->m->set_input_warp_batch(body, b, hb, wb, in_labels, tgt_labels, hl, wl, maps, nmaps, mean3, std3, load_size, x_min, y_min);
+    REQUIRE((flags & ~1) == 0, "set_input_warp_batch: unknown flag bits");
+    m->m->set_input_warp_batch(body, b, hb, wb, in_labels, tgt_labels, hl, wl, maps, nmaps, mean3, std3, load_size, x_min, y_min, flags);
   });
 }
 int swn_model_get_output(swn_model* m, int slot, float* dst) {
@@ -962,6 +968,14 @@ int swn_op_affine_gather(swn_ctx* ctx, const float* src, float* dst, int b, int 
     affine_gather(ctx->c->s, src, dst, b, c, h, w, maps, nmaps);
   });
 }
+int swn_op_chain_resample(swn_ctx* ctx, const float* src, float* dst, int b, int c, int h, int w, const double* maps,
+                          int nmaps) {
+  return guard([&] {
+    REQUIRE(ctx && src && dst && maps, "NULL argument");
+    REQUIRE(src != dst, "chain_resample is out of place");
+    chain_resample(ctx->c->s, src, dst, b, c, h, w, maps, nmaps);
+  });
+}
 int swn_op_texture_batch(swn_ctx* ctx, const uint8_t* img, int b, int hs, int ws, const uint8_t* labels, int hl, int wl,
                          const float* rois_raw, int r, const float* sample, const float* mean3, const float* std3, int x_min,
                          int y_min, int h, int w, int cloth_channels, float* in_nchw, float* tgt_nchw, float* cloths_nchw,
@@ -999,8 +1013,16 @@ int swn_op_resize_u8(swn_ctx* ctx, const uint8_t* src, size_t src_bytes, const i
 int swn_op_warp_batch(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int hl,
                       int wl, const double* maps, int nmaps, const float* mean3, const float* std3, int load_size, int x_min, int y_min,
                       int h, int w, int cloth_channels, float* bodys_nchw, float* input_cloths_nchw, float* target_cloths_nchw) {
+  return swn_op_warp_batch_ex(ctx, body, b, hb, wb, in_labels, tgt_labels, hl, wl, maps, nmaps, mean3, std3, load_size, x_min, y_min, h, w,
+                              cloth_channels, bodys_nchw, input_cloths_nchw, target_cloths_nchw, 0);
+}
+int swn_op_warp_batch_ex(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int hl,
+                         int wl, const double* maps, int nmaps, const float* mean3, const float* std3, int load_size, int x_min, int y_min,
+                         int h, int w, int cloth_channels, float* bodys_nchw, float* input_cloths_nchw, float* target_cloths_nchw,
+                         int flags) {
   return guard([&] {
     REQUIRE(ctx && body && in_labels && mean3 && std3 && bodys_nchw && input_cloths_nchw, "NULL argument");
+    REQUIRE((flags & ~1) == 0, "warp_batch: unknown flag bits");
     REQUIRE(!target_cloths_nchw || tgt_labels, "warp_batch: target cloths asked for without target label maps");
     REQUIRE(b > 0 && h > 0 && w > 0, "warp_batch: empty sizes");
     REQUIRE(cloth_channels >= 2 && cloth_channels <= 64, "warp_batch: cloth channels in [2,64]");
@@ -1012,7 +1034,7 @@ int swn_op_warp_batch(swn_ctx* ctx, const uint8_t* body, int b, int hb, int wb, 
     WarpBatchArgs a;
     a.body = body; a.Hb = hb; a.Wb = wb; a.in_labels = in_labels; a.Hl = hl; a.Wl = wl; a.maps = maps; a.nmaps = nmaps;
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.std[c] = std3[c]; }
-    a.Ls = load_size; a.x_min = x_min; a.y_min = y_min; a.C = cloth_channels;
+    a.Ls = load_size; a.x_min = x_min; a.y_min = y_min; a.C = cloth_channels; a.bicubic = (flags & 1) != 0;
     a.body_out[0] = t.v.slice(0, 4); a.nbody = 1; a.in_cloth = t.v.slice(4, cp);
     if (target_cloths_nchw) { a.tgt_labels = tgt_labels; a.tgt_cloth = t.v.slice(4 + cp, cp); }
     warp_batch(tmp.s, a);

@@ -1598,7 +1598,7 @@ void Model::set_input_texture_sources(const uint8_t*, size_t, const int64_t*, in
   throw Error(1, "set_input_texture_sources: only the texture model takes a texture batch");
 }
 void Model::set_input_warp_batch(const uint8_t*, int, int, int, const uint8_t*, const uint8_t*, int, int, const double*, int, const float*,
-                                 const float*, int, int, int) {
+                                 const float*, int, int, int, int) {
   throw Error(1, "set_input_warp_batch: only the warp model takes a warp batch");
 }
 void Model::perceptual(const float*, const float*, int, float*, float, float, float*) {
@@ -1805,6 +1805,95 @@ __attribute__((weak)) void texture_batch(Stream&, const TextureBatchArgs& a) {
   }
 }
 
+// Host form of chain_resample.h's chain_value (ops.h chain_resample): one chain at one output pixel, the same expressions in the same
+// order, a tap at a time instead of the sixteen together.  src(index) is the image's value at flat index y * W + x.
+namespace {
+template <class Src>
+float chain_value_host(const double* rows, int nmaps, int x0, int y0, int W, int H, Src src) {
+  // (volatile: one rounded operation per step, whatever the compiler's contraction rules)
+  auto dadd = [](double x, double y) { volatile double r = x + y; return (double)r; };
+  auto dsub = [](double x, double y) { volatile double r = x - y; return (double)r; };
+  auto dmul = [](double x, double y) { volatile double r = x * y; return (double)r; };
+  auto fadd = [](float x, float y) { volatile float r = x + y; return (float)r; };
+  auto fsub = [](float x, float y) { volatile float r = x - y; return (float)r; };
+  auto fmul = [](float x, float y) { volatile float r = x * y; return (float)r; };
+  auto pil_floor = [](double v) { return v < 0.0 ? (int)std::floor(v) : (int)v; };
+  auto perspective_src = [&](const double* m, long long x, long long y, double& fx, double& fy) {
+    const double xc = (double)x + 0.5, yc = (double)y + 0.5;
+    const double den = dadd(dadd(dmul(m[7], xc), dmul(m[8], yc)), 1.0);
+    fx = dadd(dadd(dmul(m[1], xc), dmul(m[2], yc)), m[3]) / den;
+    fy = dadd(dadd(dmul(m[4], xc), dmul(m[5], yc)), m[6]) / den;
+  };
+  auto nearest_step = [&](const double* m, long long& x, long long& y) {
+    const int kind = (int)m[0];
+    long long xin = x, yin = y;
+    if (kind == 1) {
+      xin = ((long long)m[3] + (long long)m[2] * y + (long long)m[1] * x) >> 16;
+      yin = ((long long)m[6] + (long long)m[5] * y + (long long)m[4] * x) >> 16;
+    } else if (kind == 2 || kind == 3) {
+      double fx, fy;
+      perspective_src(m, x, y, fx, fy);
+      xin = fx < 0.0 ? -1 : (long long)(int)fx;
+      yin = fy < 0.0 ? -1 : (long long)(int)fy;
+    }
+    x = xin; y = yin;
+    return xin >= 0 && xin < W && yin >= 0 && yin < H;
+  };
+  auto horner = [&](double p1, double p2, double p3, double p4, double d) {
+    return dadd(p1, dmul(d, dadd(p2, dmul(d, dadd(p3, dmul(d, p4))))));
+  };
+  auto cubic_taps = [&](float v1, float v2, float v3, float v4, double d) {
+    return horner((double)v2, (double)fadd(-v1, v3), (double)fsub(fadd(fmul(2.f, fsub(v1, v2)), v3), v4),
+                  (double)fadd(fsub(fadd(-v1, v2), v3), v4), d);
+  };
+  auto cubic_rows = [&](double v1, double v2, double v3, double v4, double d) {
+    return horner(v2, dadd(-v1, v3), dsub(dadd(dmul(2.0, dsub(v1, v2)), v3), v4), dadd(dsub(dadd(-v1, v2), v3), v4), d);
+  };
+  long long x = x0, y = y0;
+  int k = nmaps - 1;
+  for (; k >= 0; --k) {
+    const double* m = rows + (size_t)k * 9;
+    if ((int)m[0] == 3) break;
+    if (!nearest_step(m, x, y)) return 0.f;
+  }
+  if (k < 0) return src((int)y * W + (int)x);
+  double fx, fy;
+  perspective_src(rows + (size_t)k * 9, x, y, fx, fy);
+  const int ix = pil_floor(fx), iy = pil_floor(fy);
+  if (ix < 0 || ix >= W || iy < 0 || iy >= H) return 0.f;
+  fx = dsub(fx, 0.5); fy = dsub(fy, 0.5);
+  const int wx = pil_floor(fx), wy = pil_floor(fy);
+  const double dx = dsub(fx, (double)wx), dy = dsub(fy, (double)wy);
+  auto tap = [&](int tx, int ty) {                         // through the rows in front of the kind-3 row; 0 where it leaves the image
+    long long px = tx, py = ty;
+    for (int r = k - 1; r >= 0; --r)
+      if (!nearest_step(rows + (size_t)r * 9, px, py)) return 0.f;
+    return (float)src((int)py * W + (int)px);
+  };
+  double rv[4];
+  for (int j = 0; j < 4; ++j) {
+    const int yy = wy - 1 + j;
+    if (j > 0 && !(yy >= 0 && yy < H)) { rv[j] = rv[j - 1]; continue; }
+    const int yc = std::min(std::max(yy, 0), H - 1);
+    float v[4];
+    for (int i = 0; i < 4; ++i) v[i] = tap(std::min(std::max(wx - 1 + i, 0), W - 1), yc);
+    rv[j] = cubic_taps(v[0], v[1], v[2], v[3], dx);
+  }
+  return (float)cubic_rows(rv[0], rv[1], rv[2], rv[3], dy);
+}
+}  // namespace
+
+// Host form of ops.h chain_resample, weak like texture_batch above.
+__attribute__((weak)) void chain_resample(Stream&, const float* src, float* dst, int B, int C, int H, int W, const double* maps, int nmaps) {
+  chain_resample_check(B, C, H, W, nmaps);
+  for (int bc = 0; bc < B * C; ++bc) {
+    const float* img = src + (size_t)bc * H * W;
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x)
+        dst[((size_t)bc * H + y) * W + x] = chain_value_host(maps + (size_t)bc * nmaps * 9, nmaps, x, y, W, H, [&](int idx) { return img[idx]; });
+  }
+}
+
 // Host form of the warp batch hand-over (ops.h warp_batch), weak like texture_batch above: the same expressions in the same order as
 // warp_batch.hip.
 __attribute__((weak)) void warp_batch(Stream&, const WarpBatchArgs& a) {
@@ -1875,6 +1964,11 @@ __attribute__((weak)) void warp_batch(Stream&, const WarpBatchArgs& a) {
         for (int c = 0; c < Cp; ++c) {
           dst[c] = 0.f;
           if (c == 0 || c >= a.C) continue;
+          if (a.bicubic) {                               // the table may hold kind 3: the chain by chain_resample's rule on the indicators
+            auto hot = [&](int idx) { return a.in_labels[lb + idx] == c ? 1.f : 0.f; };
+            dst[c] = nmaps ? chain_value_host(a.maps + (size_t)(b * a.C + c) * nmaps * 9, nmaps, lx, ly, a.Wl, a.Hl, hot) : hot(ly * a.Wl + lx);
+            continue;
+          }
           const int src = walk(b * a.C + c, lx, ly);
           if (src >= 0 && a.in_labels[lb + src] == c) dst[c] = 1.f;
         }

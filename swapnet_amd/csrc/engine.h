@@ -439,7 +439,7 @@ class Model {
   // the model's H x W at (x_min, y_min) of the load_size x load_size resized sample; tgt_labels may be in_labels, NULL for inference
   virtual void set_input_warp_batch(const uint8_t* body, int N, int Hb, int Wb, const uint8_t* in_labels, const uint8_t* tgt_labels,
                                     int Hl, int Wl, const double* maps, int nmaps, const float mean[3], const float std_[3],
-                                    int load_size, int x_min, int y_min);
+                                    int load_size, int x_min, int y_min, int flags);      // flags bit 0: WarpBatchArgs::bicubic
   virtual void get_output(int slot, float* dev_nchw) = 0;
   virtual TView output_view() = 0;              // NHWC view of self.fakes (logical channels: cloth_channels warp / 3 texture)
   virtual int output_channels() const = 0;

@@ -3,6 +3,7 @@
 // SURVEY.md Appendix B), nn.functional.interpolate nearest (:244-247), MaxPool2d(2,2) of
 // VGG16 (modules/losses/perceptual.py:26-42), util/decode_labels.py:24-55,
 // datasets/data_utils.py:311-343.
+#include "chain_resample.h"
 #include "hip_util.h"
 
 namespace swn {
@@ -377,6 +378,25 @@ void affine_gather(Stream& s, const float* src, float* dst, int B, int C, int H,
   if (nmaps < 1) throw Error(1, "affine_gather: need at least one map per channel");
   hipLaunchKernelGGL(affine_gather_kernel, dim3(egrid((size_t)B * C * H * W)), dim3(256), 0, hs(s), src, dst, B * C, H, W, maps, nmaps);
   check_launch("affine_gather");
+}
+
+// ops.h chain_resample: affine_gather with kind 3 (Pillow's BICUBIC perspective) in the table.  One lane per output element like
+// affine_gather_kernel; the lanes of a wave share a channel's chain over most of a wave (64 consecutive pixels of one row), so the
+// branch on a row's kind is all but uniform here.
+__global__ __launch_bounds__(256) void chain_resample_kernel(const float* src, float* dst, int BC, int H, int W, const double* maps,
+                                                             int nmaps) {
+  const size_t total = (size_t)BC * H * W;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int x0 = (int)(i % W); const size_t q = i / W;
+    const int y0 = (int)(q % H); const int bc = (int)(q / H);
+    const float* img = src + (size_t)bc * H * W;
+    dst[i] = chain_value(maps + (size_t)bc * nmaps * 9, nmaps, x0, y0, W, H, [&](int idx) { return img[idx]; });
+  }
+}
+void chain_resample(Stream& s, const float* src, float* dst, int B, int C, int H, int W, const double* maps, int nmaps) {
+  chain_resample_check(B, C, H, W, nmaps);
+  hipLaunchKernelGGL(chain_resample_kernel, dim3(egrid((size_t)B * C * H * W)), dim3(256), 0, hs(s), src, dst, B * C, H, W, maps, nmaps);
+  check_launch("chain_resample");
 }
 
 void nchw_to_nhwc(Stream& s, const float* src, int N, int C, int H, int W, const TView& dst) {

@@ -309,14 +309,14 @@ class WarpModel final : public Model {
   // three amax passes refresh_input_slots makes for them (the conditional-D buffer's once)
   void set_input_warp_batch(const uint8_t* body_u8, int N, int Hb, int Wb, const uint8_t* in_labels, const uint8_t* tgt_labels, int Hl, int Wl,
                             const double* maps, int nmaps, const float mean[3], const float std_[3], int load_size, int x_min,
-                            int y_min) override {
+                            int y_min, int flags) override {
     if (N != B) throw Error(1, "set_input_warp_batch: shape mismatch with the model's batch");
     if (Cb != 3) throw Error(1, "set_input_warp_batch: the body is an RGB image here; this model has " + std::to_string(Cb) + " body channels");
     if (is_train && !tgt_labels) throw Error(1, "set_input_warp_batch: a training model needs the target label maps");
     WarpBatchArgs a;
     a.body = body_u8; a.Hb = Hb; a.Wb = Wb; a.in_labels = in_labels; a.Hl = Hl; a.Wl = Wl; a.maps = maps; a.nmaps = nmaps;
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std_[c]; }
-    a.Ls = load_size; a.x_min = x_min; a.y_min = y_min; a.C = Cc;
+    a.Ls = load_size; a.x_min = x_min; a.y_min = y_min; a.C = Cc; a.bicubic = (flags & 1) != 0;
     a.in_cloth = cloth.v.slice(0, Ccp);
     a.body_out[0] = body.v.slice(0, Cbp);
     a.body_out[1] = Dx.batch(0, B).v.slice(Ccp, Cbp);

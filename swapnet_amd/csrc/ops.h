@@ -421,6 +421,33 @@ void roi_align_indices(Stream& s, const float* rois, int K, int H, int W, int PH
 // A source coordinate outside the image at ANY step yields 0 (PIL's fill), like the sequential PIL calls.
 void affine_gather(Stream& s, const float* src, float* dst, int B, int C, int H, int W, const double* maps, int nmaps);
 
+// affine_gather with one more kind in the table (gather.hip; the host loop of engine.cpp): kinds 0 to 2 as above, and
+//   kind 3 -- perspective resampled BICUBIC, bit-identical to Pillow's Image.transform(size, PERSPECTIVE, c0..c7, BICUBIC) on a mode-"F"
+//             image, which is what torchvision 0.4.0's RandomPerspective does to a channel of per_channel_transform
+//             (datasets/data_utils.py:346-361).  c0..c7 as for kind 2.  In IEEE double unless said otherwise, one rounded operation per
+//             step, no FMA contraction.  For output pixel (x, y):
+//               xc = x + .5, yc = y + .5;  den = c6 xc + c7 yc + 1;  fx = (c0 xc + c1 yc + c2) / den;  fy = (c3 xc + c4 yc + c5) / den
+//               FLOOR(v) = (int)floor(v) for v < 0, else (int)v.  FLOOR(fx) outside [0, W) or FLOOR(fy) outside [0, H): the output is 0.
+//               fx -= .5, fy -= .5;  x0 = FLOOR(fx), y0 = FLOOR(fy);  dx = fx - x0, dy = fy - y0;  the window starts at (x0 - 1, y0 - 1);
+//               its four column indices are each clipped to [0, W - 1].
+//               cub(v1, v2, v3, v4, d) = p1 + d (p2 + d (p3 + d p4)),  p1 = v2, p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4,
+//               p4 = -v1 + v2 - v3 + v4, every sum left to right.
+//               Row 0 of the window uses its row index clipped to [0, H - 1]; rows 1 to 3 are evaluated only where their index lies inside
+//               the image, an outside row takes the previous row's value.  A row's value is cub(its four texels, dx), where p2, p3 and p4
+//               are FP32 expressions of the fp32 texels (Pillow's macro is handed the FLOAT32 lvalues: each operation rounds to
+//               fp32; on 0/1 maps this is exact either way) and p1 and the Horner form in d are double.  The pixel is
+//               (float)cub(r0, r1, r2, r3, dy), all in double.
+// A chain is evaluated as for affine_gather: the rows behind the kind-3 row are walked first from the output pixel, and the rows in
+// front of it define the image the sixteen taps read -- each tap walks them backwards with the NEAREST rule, and a tap that leaves the
+// image anywhere on the way reads 0.  PRECONDITION: at most one kind-3 row per chain (what one RandomOrder draw can produce; the
+// Python layer refuses more); a further one would be resampled NEAREST like kind 2, and nothing is read or written out of bounds.
+// Coefficients are those of the transform's own draw: finite, |fx|, |fy| < 2^31.  A table without kind 3 gives affine_gather's bytes.
+void chain_resample(Stream& s, const float* src, float* dst, int B, int C, int H, int W, const double* maps, int nmaps);
+inline void chain_resample_check(int B, int C, int H, int W, int nmaps) {
+  if (nmaps < 1) throw Error(1, "chain_resample: need at least one map per channel");
+  if (B < 1 || C < 1 || H < 1 || W < 1 || (size_t)H * (size_t)W > 0x7fffffffu) throw Error(1, "chain_resample: empty or oversized image");
+}
+
 // layout conversion at the Python boundary (NCHW fp32 <-> NHWC view)
 void nchw_to_nhwc(Stream& s, const float* src, int N, int C, int H, int W, const TView& dst);
 void nhwc_to_nchw(Stream& s, const TView& src, float* dst, int C);
@@ -533,10 +560,15 @@ inline void resize_u8_check(const ResizeU8Args& a) {
 // all in fp32, one correctly rounded operation per step (no FMA contraction), pad channels of every view written as zero.
 // tgt_labels may be in_labels (--dataset_mode image); tgt_cloth may be empty (inference: nothing of a target is read or written).
 // Every view must be 16-byte tileable (C % 4, cs % 4, aligned base).
+// `bicubic` says that the table may hold kind 3 (chain_resample above): in_cloth[b,y,x,c] is then channel c's chain evaluated by
+// chain_resample's rule at (nearest(sy), nearest(sx)) of the Hl x Wl map, the texels being the indicators in_labels == c (0 for c = 0) --
+// a float that need not be 0 or 1.  It selects another instantiation of the kernel; without it the launch is the one it always was and
+// kind 3 must not occur.  The body and target outputs do not depend on it.
 struct WarpBatchArgs {
   const uint8_t* body = nullptr; int Hb = 0, Wb = 0;                          // (B,Hb,Wb,3)
   const uint8_t* in_labels = nullptr; const uint8_t* tgt_labels = nullptr; int Hl = 0, Wl = 0;       // (B,Hl,Wl) each
   const double* maps = nullptr; int nmaps = 0;                                // [B*C][nmaps][9]; nmaps 0: no augmentation
+  bool bicubic = false;                                                       // the table may hold kind 3
   float mean[3] = {0.f, 0.f, 0.f}, std[3] = {1.f, 1.f, 1.f}; int Ls = 0, x_min = 0, y_min = 0; int C = 0;   // C = cloth channels
   TView in_cloth, tgt_cloth;                                                  // C padded to a multiple of 4; tgt_cloth may be empty
   TView body_out[3]; int nbody = 0;                                           // one to three 4-channel destinations of the body

@@ -14,6 +14,7 @@
 // host chain never exists.
 #include <algorithm>
 
+#include "chain_resample.h"
 #include "hip_util.h"
 
 namespace swn {
@@ -67,10 +68,44 @@ __device__ __forceinline__ int walk(const WBp& p, int bc, int x0, int y0) {
   return (int)y * p.Wl + (int)x;
 }
 
-__global__ __launch_bounds__(256) void warp_batch_kernel(const WBp p) {
-  const int Q = 1 + 2 * p.Cq;
-  const size_t nunit = (size_t)p.B * p.H * p.W * Q, stride = (size_t)gridDim.x * 256;
+// BICUBIC = false: the table holds kinds 0 to 2, the work units above.  BICUBIC = true (WarpBatchArgs::bicubic): it may hold kind 3,
+// and an input-cloth value is then a chain evaluated by chain_resample.h -- up to 16 taps through up to nmaps - 1 rows and two cubics in
+// double, against one walk.  The four channels of a cloth unit would run that one after the other on one lane, while the body and
+// target lanes of the wave wait and the chains of the wave's channels differ in kind.  So that instantiation splits the index space
+// in two: first the 1 + Cq body and target units of every pixel, as above, padded to a whole number of blocks; then ONE LANE PER
+// (pixel, channel), four consecutive lanes a 16-byte group.  A lane evaluates its channel's whole chain by itself -- the order of
+// rounded operations per output is the rule's -- the four values of a group meet in its first lane through ds_bpermute (__shfl, width
+// 4), and that lane stores the float4.  Both ranges start on a multiple of 256 and the grid stride is one, so a group never
+// straddles a wave and its four lanes leave the loop together.  (The second launch bound holds <true> to four waves per SIMD: 123 VGPRs
+// where the allocator would take 129; <false> keeps the allocation it always had, 56.)
+template <bool BICUBIC>
+__global__ __launch_bounds__(256, BICUBIC ? 4 : 1) void warp_batch_kernel(const WBp p) {
+  const int Q = BICUBIC ? 1 + p.Cq : 1 + 2 * p.Cq;
+  const size_t npix = (size_t)p.B * p.H * p.W;
+  const size_t nlight = npix * Q, nlight_pad = BICUBIC ? (nlight + 255) / 256 * 256 : nlight;
+  const size_t nunit = BICUBIC ? nlight_pad + npix * 4 * p.Cq : nlight, stride = (size_t)gridDim.x * 256;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nunit; i += stride) {
+    if constexpr (BICUBIC) {
+      if (i >= nlight_pad) {                             // ---- one channel of the augmented input cloth
+        const size_t e = i - nlight_pad;
+        const int Cp = 4 * p.Cq;
+        const size_t pix = e / Cp;
+        const int c = (int)(e - pix * Cp);
+        const int x = (int)(pix % p.W); const size_t t = pix / p.W;
+        const int y = (int)(t % p.H); const int b = (int)(t / p.H);
+        const int ly = nearest_src(p.y_min + y, p.lscale_y, p.Hl), lx = nearest_src(p.x_min + x, p.lscale_x, p.Wl);
+        const uint8_t* lab = p.in_labels + (size_t)b * p.Hl * p.Wl;
+        float v = 0.f;
+        if (c != 0 && c < p.C) {
+          auto hot = [&](int idx) { return lab[idx] == c ? 1.f : 0.f; };
+          v = p.nmaps ? chain_value(p.maps + (size_t)(b * p.C + c) * p.nmaps * 9, p.nmaps, lx, ly, p.Wl, p.Hl, hot) : hot(ly * p.Wl + lx);
+        }
+        const float v1 = __shfl(v, 1, 4), v2 = __shfl(v, 2, 4), v3 = __shfl(v, 3, 4);
+        if ((c & 3) == 0) *reinterpret_cast<float4*>(p.in_cloth + pix * p.in_cs + c) = make_float4(v, v1, v2, v3);
+        continue;
+      }
+      if (i >= nlight) continue;                         // (the pad between the two ranges)
+    }
     const size_t pix = i / Q;
     const int u = (int)(i - pix * Q);
     const int x = (int)(pix % p.W); const size_t t = pix / p.W;
@@ -103,7 +138,7 @@ __global__ __launch_bounds__(256) void warp_batch_kernel(const WBp p) {
       const int hot = (l != 0 && l < p.C) ? l - c0 : -1;       // label 0 -> the all-zero vector; pad channels stay zero
       *reinterpret_cast<float4*>(p.tgt_cloth + pix * p.tgt_cs + c0) =
           make_float4(hot == 0 ? 1.f : 0.f, hot == 1 ? 1.f : 0.f, hot == 2 ? 1.f : 0.f, hot == 3 ? 1.f : 0.f);
-    } else {                                             // ---- four channels of the augmented input cloth
+    } else if constexpr (!BICUBIC) {                     // ---- four channels of the augmented input cloth
       const int c0 = (u - 1 - p.Cq) * 4;
       float v[4];
 #pragma unroll
@@ -133,9 +168,17 @@ void warp_batch(Stream& s, const WarpBatchArgs& a) {
   for (int c = 0; c < 3; ++c) { p.mean[c] = a.mean[c]; p.sd[c] = a.std[c]; }
   p.lscale_y = (float)a.Hl / (float)a.Ls; p.lscale_x = (float)a.Wl / (float)a.Ls;
   p.bscale_y = (float)a.Hb / (float)a.Ls; p.bscale_x = (float)a.Wb / (float)a.Ls;
-  const size_t total = (size_t)p.B * p.H * p.W * (1 + 2 * p.Cq);
+  const size_t npix = (size_t)p.B * p.H * p.W;
+  if (a.bicubic) {                                        // (the kernel's two index ranges)
+    const size_t total = (npix * (1 + p.Cq) + 255) / 256 * 256 + npix * 4 * p.Cq;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
+    hipLaunchKernelGGL(warp_batch_kernel<true>, dim3(grid), dim3(256), 0, hs(s), p);
+    check_launch("warp_batch (bicubic)");
+    return;
+  }
+  const size_t total = npix * (1 + 2 * p.Cq);
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(warp_batch_kernel, dim3(grid), dim3(256), 0, hs(s), p);
+  hipLaunchKernelGGL(warp_batch_kernel<false>, dim3(grid), dim3(256), 0, hs(s), p);
   check_launch("warp_batch");
 }
 

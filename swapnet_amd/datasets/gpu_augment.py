@@ -6,13 +6,17 @@ RandomHorizontalFlip, RandomAffine(degrees=10, translate=(.1,.1), scale=(.8,1.2)
 (/root/reference/datasets/warp_dataset.py:131-137, datasets/__init__.py:87-110, datasets/data_utils.py:346-361):
 19 channels x up to 4 PIL resamplings per sample, every training step.  Here the random PARAMETERS are drawn on the
 host exactly like torchvision 0.4.0's transforms draw them (same `random` calls in the same order), turned into
-inverse pixel maps, and ONE device kernel (swn_op_affine_gather) applies every chain of the whole batch.
+inverse pixel maps, and ONE device kernel (swn_op_affine_gather, or swn_op_chain_resample where a table holds the
+bicubic kind) applies every chain of the whole batch.
 
 Exactness: flips and RandomAffine use PIL's NEAREST rule in Pillow's own 16.16 fixed point -> bit-identical to the
 reference's per-channel PIL calls given the same parameters (tests/test_augment.py compares against Pillow itself).
-RandomPerspective is resampled with NEAREST here; torchvision 0.4.0 resamples it BICUBIC and fits its coefficients
-with a float32 least-squares solve, neither of which is reproducible bit for bit -- this is the one documented
-deviation (a one-hot channel stays binary here, which is what the segmentation means).
+RandomPerspective is resampled NEAREST by default (a one-hot channel stays binary, which is what the segmentation
+means).  torchvision 0.4.0 resamples it BICUBIC: `perspective_resample="bicubic"` is that, opt-in, bit-identical to
+Pillow's mode-"F" Image.transform(PERSPECTIVE, BICUBIC) given the same coefficients (tests/test_augment_bicubic.py;
+the channel then holds values between about -0.3 and 1.3).  What remains unpinned is torchvision's float32
+least-squares fit of the coefficients (torch 1.2's LAPACK; here they are solved in float64) -- the one documented
+deviation.
 """
 import math
 import random
@@ -23,6 +27,24 @@ import torch
 from .. import _C, engine
 
 KIND_IDENTITY, KIND_AFFINE, KIND_PERSPECTIVE = 0, 1, 2
+KIND_PERSPECTIVE_BICUBIC = 3                       # the coefficients of kind 2, resampled like Pillow's BICUBIC
+PERSPECTIVE_RESAMPLE = ("nearest", "bicubic")
+
+
+def check_perspective_resample(value):
+    if value not in PERSPECTIVE_RESAMPLE:
+        raise ValueError("perspective_resample must be one of %s, got %r" % (PERSPECTIVE_RESAMPLE, value))
+    return value
+
+
+def has_bicubic(maps):
+    """Whether a (..., nmaps, 9) table holds the bicubic kind; more than one such row in a chain is refused (one RandomOrder draw
+    cannot produce it, and the kernels evaluate one)."""
+    kinds = np.asarray(maps)[..., 0]
+    per_chain = (kinds == KIND_PERSPECTIVE_BICUBIC).sum(axis=-1)
+    if per_chain.size and int(per_chain.max()) > 1:
+        raise ValueError("map table: at most one bicubic perspective row (kind 3) per chain, found %d" % int(per_chain.max()))
+    return bool(per_chain.any())
 
 
 def _fix(v):
@@ -96,9 +118,13 @@ def random_perspective_points(W, H, distortion_scale=0.5, rng=random):
 
 class GpuPerChannelTransform:
     """Drop-in for `per_channel_transform(tensor, get_transforms(opt))` on a whole BATCH that already sits on the device.
-    `input_transforms` uses the reference's option values ("hflip", "vflip", "affine", "perspective", "all", "none")."""
+    `input_transforms` uses the reference's option values ("hflip", "vflip", "affine", "perspective", "all", "none").
+    `perspective_resample`: "nearest" (the default) or "bicubic" (what torchvision 0.4.0 does); the draws are the same calls in the
+    same order, only the kind of the perspective rows differs."""
 
-    def __init__(self, input_transforms=("hflip", "vflip", "affine", "perspective"), ctx=None, rng=random):
+    def __init__(self, input_transforms=("hflip", "vflip", "affine", "perspective"), ctx=None, rng=random, perspective_resample="nearest"):
+        self.perspective_resample = check_perspective_resample(perspective_resample)
+        self.perspective_kind = KIND_PERSPECTIVE_BICUBIC if perspective_resample == "bicubic" else KIND_PERSPECTIVE
         t = [input_transforms] if isinstance(input_transforms, str) else list(input_transforms)
         every = "all" in t
         # datasets/__init__.py:get_transforms appends in this order
@@ -128,7 +154,7 @@ class GpuPerChannelTransform:
             else:
                 if rng.random() < 0.5:
                     sp, ep = random_perspective_points(W, H, rng=rng)
-                    chain.append([KIND_PERSPECTIVE] + perspective_coeffs(sp, ep))
+                    chain.append([self.perspective_kind] + perspective_coeffs(sp, ep))
                 else:
                     chain.append(IDENTITY)
         return chain
@@ -148,12 +174,14 @@ class GpuPerChannelTransform:
 
 
 def apply_maps(ctx, batch, maps):
-    """maps: array (B, C, nmaps, 9) of {kind, c0..c7} rows; see include/swapnet_hip.h swn_op_affine_gather."""
+    """maps: array (B, C, nmaps, 9) of {kind, c0..c7} rows; see include/swapnet_hip.h swn_op_affine_gather, and
+    swn_op_chain_resample for a table that holds kind 3 (at most one such row per chain: more is a ValueError)."""
     B, C, H, W = batch.shape
     maps = np.ascontiguousarray(maps, dtype=np.float64).reshape(B * C, -1, 9)
+    op = "swn_op_chain_resample" if has_bicubic(maps) else "swn_op_affine_gather"
     src = batch.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
     dst = torch.empty_like(src)
     md = torch.from_numpy(maps).to(ctx.device)
-    ctx.lib.call("swn_op_affine_gather", ctx.handle, _C.ptr(src), _C.ptr(dst), B, C, H, W, _C.ptr(md), maps.shape[1])
+    ctx.lib.call(op, ctx.handle, _C.ptr(src), _C.ptr(dst), B, C, H, W, _C.ptr(md), maps.shape[1])
     ctx.sync()
     return dst

@@ -14,8 +14,10 @@ draws them (the same `random` calls in the same order as torchvision's transform
 
 A sample without "input_labels_u8" takes its target map as the input (--dataset_mode image, and inference); in video mode the
 dataset picks another frame's map and passes it.  What stays on the host: the PIL decode of the body and the .npz decompression.
-Exactness is that of gpu_augment: flips and RandomAffine are bit-identical to the per-channel PIL calls, RandomPerspective is
-resampled NEAREST where torchvision 0.4.0 resamples BICUBIC (the one documented deviation); the body is torch's published bilinear
+Exactness is that of gpu_augment: flips and RandomAffine are bit-identical to the per-channel PIL calls; RandomPerspective is
+resampled NEAREST by default, and with `perspective_resample="bicubic"` (opt-in: `opt.perspective_resample` or the keyword) BICUBIC
+like torchvision 0.4.0 does, bit-identical to Pillow given the same coefficients -- what remains unpinned is torchvision's float32
+least-squares fit of them (the one documented deviation); the body is torch's published bilinear
 formula in fp32, one rounded operation per step (torch's own vectorised CPU kernel differs from that by a few ulp, and from
 itself between thread counts).  The maps of a batch are drawn after all its samples were loaded, sample-major and channel-minor:
 the order a single-worker reference loader consumes `random` in image mode.
@@ -26,16 +28,18 @@ import numpy as np
 import torch
 
 from .. import engine
-from .gpu_augment import GpuPerChannelTransform
+from .gpu_augment import GpuPerChannelTransform, check_perspective_resample, has_bicubic
 from .gpu_texture_batch import GpuTextureBatch
 
 
 def expand_batch(ctx, batch, cloth_channels=19, targets=True):
-    """Compact batch -> the reference-form dict (tensors on the context's device), through swn_op_warp_batch."""
+    """Compact batch -> the reference-form dict (tensors on the context's device), through swn_op_warp_batch (swn_op_warp_batch_ex
+    where the batch carries perspective_resample "bicubic")."""
     x_min, y_min, width, height = batch["crop"]
     mean, std = batch["norm_stats"]
     bodys, inputs, tgts = engine.op_warp_batch(ctx, batch["bodys_u8"], batch["input_labels_u8"], batch["target_labels_u8"] if targets else None,
-                                               batch.get("maps"), mean, std, batch["load_size"], x_min, y_min, height, width, cloth_channels)
+                                               batch.get("maps"), mean, std, batch["load_size"], x_min, y_min, height, width, cloth_channels,
+                                               bicubic=engine.warp_batch_bicubic(batch))
     out = {"body_paths": batch["body_paths"], "bodys": bodys, "cloth_paths": batch["cloth_paths"], "input_cloths": inputs}
     if targets:
         out["target_cloths"] = tgts
@@ -45,14 +49,18 @@ def expand_batch(ctx, batch, cloth_channels=19, targets=True):
 class GpuWarpBatch:
     """Collates warp samples in compact form.  `opt` carries the reference's options: `input_transforms` ("none", "hflip", "vflip",
     "affine", "perspective", "all"), `load_size`, `crop_size` / `crop_bounds`, `body_norm_stats`, `cloth_channels` and `is_train`
-    (an inference batch is not augmented, warp_dataset.py:114-116)."""
+    (an inference batch is not augmented, warp_dataset.py:114-116), and `perspective_resample` ("nearest", the default, or "bicubic")
+    where present; the keyword of the same name overrides it."""
 
     _parse_crop_bounds = staticmethod(GpuTextureBatch._parse_crop_bounds)
 
-    def __init__(self, opt, ctx=None, rng=random):
+    def __init__(self, opt, ctx=None, rng=random, perspective_resample=None):
         self.opt, self.ctx, self.rng = opt, ctx, rng
         self.is_train = bool(getattr(opt, "is_train", True))
-        self.transform = GpuPerChannelTransform(getattr(opt, "input_transforms", "none"), rng=rng)
+        if perspective_resample is None:
+            perspective_resample = getattr(opt, "perspective_resample", "nearest")
+        self.perspective_resample = check_perspective_resample(perspective_resample)
+        self.transform = GpuPerChannelTransform(getattr(opt, "input_transforms", "none"), rng=rng, perspective_resample=perspective_resample)
         self.load_size = int(opt.load_size)
         self.crop_bounds = self._parse_crop_bounds(opt)
         self.cloth_channels = int(getattr(opt, "cloth_channels", 19))
@@ -62,7 +70,8 @@ class GpuWarpBatch:
     def collate(self, samples, maps=None):
         """samples: dicts {body_u8 (Hb,Wb,3) uint8 = the decoded RGB body image, target_labels_u8 (Hl,Wl) uint8 = the stored cloth
         label map, optional input_labels_u8 (Hl,Wl) uint8 = the map to augment when it is another one (video mode), paths
-        (cloth_path, body_path)}.  maps: a (B, cloth_channels, nmaps, 9) table to use instead of drawing one."""
+        (cloth_path, body_path)}.  maps: a (B, cloth_channels, nmaps, 9) table to use instead of drawing one (kind 3 in it needs
+        perspective_resample "bicubic": a ValueError otherwise).  A bicubic batch carries the choice as "perspective_resample"."""
         n = len(samples)
         bodys = [np.asarray(s["body_u8"], dtype=np.uint8) for s in samples]
         tgts = [np.asarray(s["target_labels_u8"], dtype=np.uint8) for s in samples]
@@ -85,15 +94,22 @@ class GpuWarpBatch:
         if maps is None and self.is_train and self.transform.transforms:
             maps = self.transform.draw_maps(n, self.cloth_channels, wl, hl)
         if maps is not None:
-            maps = torch.from_numpy(np.ascontiguousarray(maps, dtype=np.float64).reshape(n, self.cloth_channels, -1, 9))
+            maps = np.ascontiguousarray(maps, dtype=np.float64).reshape(n, self.cloth_channels, -1, 9)
+            if has_bicubic(maps) and self.perspective_resample != "bicubic":
+                raise ValueError("warp batch: the map table holds kind 3 (bicubic perspective) but perspective_resample is %r"
+                                 % (self.perspective_resample,))
+            maps = torch.from_numpy(maps)
         if self.crop_bounds:
             (x_min, y_min), (x_max, y_max) = self.crop_bounds
             crop = (int(x_min), int(y_min), int(x_max - x_min), int(y_max - y_min))
         else:
             crop = (0, 0, self.load_size, self.load_size)
-        return {"bodys_u8": torch.from_numpy(np.stack(bodys)), "input_labels_u8": inputs, "target_labels_u8": target, "maps": maps,
-                "load_size": self.load_size, "crop": crop, "norm_stats": self.norm_stats,
-                "cloth_paths": [s["paths"][0] for s in samples], "body_paths": [s["paths"][1] for s in samples]}
+        batch = {"bodys_u8": torch.from_numpy(np.stack(bodys)), "input_labels_u8": inputs, "target_labels_u8": target, "maps": maps,
+                 "load_size": self.load_size, "crop": crop, "norm_stats": self.norm_stats,
+                 "cloth_paths": [s["paths"][0] for s in samples], "body_paths": [s["paths"][1] for s in samples]}
+        if self.perspective_resample != "nearest":       # (a batch without the key is a "nearest" one: the default form is unchanged)
+            batch["perspective_resample"] = self.perspective_resample
+        return batch
 
     def expand(self, batch):
         return expand_batch(self.ctx or engine.default_context(), batch, self.cloth_channels)

@@ -405,7 +405,9 @@ class NativeModel:
     def set_input_warp_batch(self, batch):
         """Warp model: bodys, input_cloths and (training) target_cloths from the compact batch dict of
         datasets.gpu_warp_batch.GpuWarpBatch.collate (uint8 body images and label maps, the per-channel map table) in one device
-        launch.  `input_labels_u8` being the very tensor `target_labels_u8` is (--dataset_mode image) is uploaded once."""
+        launch.  `input_labels_u8` being the very tensor `target_labels_u8` is (--dataset_mode image) is uploaded once.  A batch that
+        carries perspective_resample "bicubic" goes through swn_model_set_input_warp_batch_ex with flags bit 0 (its table may hold
+        kind 3, at most one row per chain); any other batch makes the call it always made."""
         tgt_src, in_src = batch["target_labels_u8"], batch["input_labels_u8"]
         names = ["bodys_u8", "input_labels_u8"] + (["target_labels_u8"] if self.is_train and tgt_src is not in_src else [])
         dev, tokens = {}, []
@@ -415,6 +417,8 @@ class NativeModel:
         body, lab = dev["bodys_u8"], dev["input_labels_u8"]
         tgt = dev.get("target_labels_u8", lab) if self.is_train else None
         maps, nmaps = _warp_maps(batch.get("maps"), body.shape[0], self.cloth_channels)
+        bicubic = warp_batch_bicubic(batch)
+        _check_warp_kinds(maps, bicubic)
         if maps is not None:
             dev["maps"], token = self.ctx.upload(maps, torch.float64, key=(id(self), "wb", "maps"))
             tokens.append(token)
@@ -424,10 +428,14 @@ class NativeModel:
         if tuple(batch["crop"][2:]) not in ((), (self.W, self.H)):
             raise ValueError("warp batch: its crop window is %s (W, H), the model's %s" % (tuple(batch["crop"][2:]), (self.W, self.H)))
         self._torch_done()
-        self.lib.call("swn_model_set_input_warp_batch", self.handle, _C.ptr(body), body.shape[0], body.shape[1], body.shape[2], _C.ptr(lab),
-                      _C.ptr(tgt) if tgt is not None else None, lab.shape[1], lab.shape[2],
-                      _C.ptr(dev["maps"]) if maps is not None else None, nmaps, (C.c_float * 3)(*mean), (C.c_float * 3)(*std),
-                      int(batch["load_size"]), int(x_min), int(y_min))
+        args = (self.handle, _C.ptr(body), body.shape[0], body.shape[1], body.shape[2], _C.ptr(lab),
+                _C.ptr(tgt) if tgt is not None else None, lab.shape[1], lab.shape[2],
+                _C.ptr(dev["maps"]) if maps is not None else None, nmaps, (C.c_float * 3)(*mean), (C.c_float * 3)(*std),
+                int(batch["load_size"]), int(x_min), int(y_min))
+        if bicubic:                         # (a "nearest" batch makes the call it always made)
+            self.lib.call("swn_model_set_input_warp_batch_ex", *args, 1)
+        else:
+            self.lib.call("swn_model_set_input_warp_batch", *args)
         self._sync_if_needed()
         for token in tokens:
             self.ctx.consumed(token)
@@ -977,6 +985,25 @@ def _warp_maps(maps, b, cloth_channels):
     return maps.to(torch.float64).reshape(b * cloth_channels, maps.shape[2], 9).contiguous(), int(maps.shape[2])
 
 
+def warp_batch_bicubic(batch):
+    """Whether a compact warp batch asks for the bicubic perspective ("perspective_resample", absent: "nearest")."""
+    choice = batch.get("perspective_resample", "nearest")
+    if choice not in ("nearest", "bicubic"):
+        raise ValueError("warp batch: perspective_resample must be 'nearest' or 'bicubic', got %r" % (choice,))
+    return choice == "bicubic"
+
+
+def _check_warp_kinds(maps, bicubic):
+    """Before any launch: kind 3 needs the bicubic instantiation, which evaluates one such row per chain."""
+    if maps is None:
+        return
+    n3 = (maps[..., 0] == 3).sum(dim=-1)
+    if int(n3.max()) > 1:
+        raise ValueError("warp batch: at most one bicubic perspective row (kind 3) per chain, found %d" % int(n3.max()))
+    if int(n3.max()) and not bicubic:
+        raise ValueError("warp batch: the map table holds kind 3 (bicubic perspective) but the batch is not a bicubic one")
+
+
 def _check_warp_batch(body, lab, tgt):
     if body.dim() != 4 or lab.dim() != 3 or (tgt is not None and tgt.dim() != 3):
         raise ValueError("warp batch: bodys_u8 (B,Hb,Wb,Cb), input_labels_u8 and target_labels_u8 (B,Hl,Wl)")
@@ -987,26 +1014,32 @@ def _check_warp_batch(body, lab, tgt):
 
 
 def op_warp_batch(ctx, bodys_u8, input_labels_u8, target_labels_u8, maps, mean, std, load_size, x_min, y_min, height, width,
-                  cloth_channels=19):
+                  cloth_channels=19, bicubic=False):
     """WarpDataset.__getitem__ for a batch through swn_op_warp_batch: (bodys, input_cloths, target_cloths) on the context's device,
     NCHW float32, from uint8 HWC body images (B,Hb,Wb,3), uint8 label maps (B,Hl,Wl) and the (B, cloth_channels, nmaps, 9) map
-    table (None: no augmentation).  target_labels_u8 None: no targets (target_cloths is None)."""
+    table (None: no augmentation).  target_labels_u8 None: no targets (target_cloths is None).  bicubic: the table may hold kind 3
+    (swn_op_warp_batch_ex, flags bit 0); off, the call is swn_op_warp_batch as it always was."""
     u8 = lambda t: torch.as_tensor(t).to(device=ctx.device, dtype=torch.uint8).contiguous()
     body, lab = u8(bodys_u8), u8(input_labels_u8)
     tgt = None if target_labels_u8 is None else (lab if target_labels_u8 is input_labels_u8 else u8(target_labels_u8))
     _check_warp_batch(body, lab, tgt)
     b = body.shape[0]
     maps, nmaps = _warp_maps(maps, b, cloth_channels)
+    _check_warp_kinds(maps, bicubic)
     md = None if maps is None else maps.to(ctx.device)
     bodys = torch.empty((b, 3, height, width), dtype=torch.float32, device=ctx.device)
     inputs = torch.empty((b, cloth_channels, height, width), dtype=torch.float32, device=ctx.device)
     targets = None if tgt is None else torch.empty_like(inputs)
     if ctx.owns_stream:                     # (the uploads above ran on torch's stream)
         torch.cuda.current_stream(ctx.device).synchronize()
-    ctx.lib.call("swn_op_warp_batch", ctx.handle, _C.ptr(body), b, body.shape[1], body.shape[2], _C.ptr(lab),
-                 _C.ptr(tgt) if tgt is not None else None, lab.shape[1], lab.shape[2], _C.ptr(md) if md is not None else None, nmaps,
-                 (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(load_size), int(x_min), int(y_min), int(height), int(width),
-                 int(cloth_channels), _C.ptr(bodys), _C.ptr(inputs), _C.ptr(targets) if targets is not None else None)
+    args = (ctx.handle, _C.ptr(body), b, body.shape[1], body.shape[2], _C.ptr(lab),
+            _C.ptr(tgt) if tgt is not None else None, lab.shape[1], lab.shape[2], _C.ptr(md) if md is not None else None, nmaps,
+            (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(load_size), int(x_min), int(y_min), int(height), int(width),
+            int(cloth_channels), _C.ptr(bodys), _C.ptr(inputs), _C.ptr(targets) if targets is not None else None)
+    if bicubic:
+        ctx.lib.call("swn_op_warp_batch_ex", *args, 1)
+    else:
+        ctx.lib.call("swn_op_warp_batch", *args)
     return bodys, inputs, targets
 
 
