@@ -42,7 +42,8 @@ int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lamb
                                 5: swn_ctx_attach_comm, swn_model_step_dp; 6: swn_probe_mfma; 7: swn_op_conv_produced, swn_slot_audit; 8: swn_op_loss, swn_op_bias_grad;
                                 9: swn_op_norm_act, swn_op_elementwise, swn_op_resample (additions since, version unchanged: swn_op_resize_u8,
                                 swn_model_set_input_texture_sources, swn_op_conv_views, swn_op_chain_resample, swn_op_warp_batch_ex,
-                                swn_model_set_input_warp_batch_ex) */
+                                swn_model_set_input_warp_batch_ex, swn_op_image_u8, swn_pipeline_enable_images, swn_pipeline_images; the PNG entry points
+                                swn_op_png_encode, swn_png_stream_bound, swn_pipeline_enable_png, swn_pipeline_png were added within ABI 9 as well) */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -313,6 +314,15 @@ int swn_pipeline_enable_images(swn_pipeline* p, const float* body_mean3, const f
  * swn_pipeline_labels' map; also the texture stage's cloths_decoded, whose cloth input is that map), textures_unnormalized with the
  * ROI outlines, fakes, fakes_scaled.  Stream-ordered behind the run: synchronise (swn_ctx_sync) before reading. */
 int swn_pipeline_images(swn_pipeline* p, uint8_t** dev, int* k);
+/* The PNG files of that sheet, encoded on the device -- what util.save_image (util/util.py:54-69: Image.fromarray(a).save(path), six
+ * times per sample) makes the host's zlib do.  Requires swn_pipeline_enable_images first (otherwise an error that says so).  An armed
+ * pipeline ends its graph with the two launches of swn_op_png_encode over the K * B images of the sheet; arming after a capture drops
+ * the graph, as swn_pipeline_enable_images does.  rows_per_chunk as in swn_op_png_encode (0 = default).  May be called again. */
+int swn_pipeline_enable_png(swn_pipeline* p, int rows_per_chunk);
+/* The streams of the last run, library-owned device memory: *streams = K * B zlib streams, *stride bytes apart, in the sheet's order
+ * (image k of sample b at index k * B + b); *sizes = their K * B lengths; *k = K = 6.  Stream-ordered behind the run: synchronise
+ * before reading.  The PNG container around a stream is host work: swapnet_amd/util/png.py png_container. */
+int swn_pipeline_png(swn_pipeline* p, uint8_t** streams, uint32_t** sizes, size_t* stride, int* k);
 
 /* Data-parallel texture stage: the style term is MSE(Gram(output), Gram(target)) with the Gram over the WHOLE batch viewed
  * as (B*C, H*W) (modules/losses/perceptual.py:6-10,58-63), so it couples the samples of all ranks.  The host all-gathers the
@@ -435,6 +445,18 @@ int swn_op_decode_labels(swn_ctx* ctx, const float* x, int b, int c, int h, int 
  *     (coordinates truncated toward zero, clipped to the image).  x1 < x0 or y1 < y0 is Pillow's ValueError: check before calling. */
 int swn_op_image_u8(swn_ctx* ctx, const float* x, int b, int c, int h, int w, const int32_t* labels, int source, const float* rows,
                     int scale_each, int range, const float* rois, int r, const uint8_t* colours, int width, uint8_t* out);
+/* The encoding half of util.save_image (util/util.py:54-69: Image.fromarray(image_numpy).save(image_path) writes a PNG): n images
+ * (h,w,3) uint8, interleaved and contiguous -- what swn_op_image_u8 writes -- to n zlib streams (RFC 1950) of the PNG-filtered
+ * scanlines, streams[i * stream_stride ...], sizes[i] bytes long.  img, streams and sizes are DEVICE pointers.  Rows are filtered by the
+ * type with the smallest sum of min(b, 256 - b) (ties to the lower type); each chunk of rows_per_chunk rows (0 = default:
+ * min(16, 32768 / (1 + 3w)), at least 1) becomes one dynamic-Huffman block with run-length matches, or a stored block where that is
+ * not larger.  w <= 2048 and rows_per_chunk * (1 + 3w) <= 32768, otherwise an error (code 1).  stream_stride >=
+ * swn_png_stream_bound(h, w, rows_per_chunk); bytes of a slot behind its stream are not written.  Signature, IHDR, IDAT and IEND are
+ * assembled on the host (swapnet_amd/util/png.py).  Synchronises.  Device library only. */
+int swn_op_png_encode(swn_ctx* ctx, const uint8_t* img, int n, int h, int w, int rows_per_chunk, uint8_t* streams, size_t stream_stride,
+                      uint32_t* sizes);
+/* No stream of swn_op_png_encode for this shape is longer than *out bytes (plain arithmetic: answered by every build). */
+int swn_png_stream_bound(int h, int w, int rows_per_chunk, size_t* out);
 /* datasets/data_utils.py:322 (argmax for compress_and_save_cloth) and :330-343 (to_onehot_tensor) */
 int swn_op_argmax_labels(swn_ctx* ctx, const float* x, int b, int c, int h, int w, int32_t* labels);
 int swn_op_labels_to_onehot(swn_ctx* ctx, const int32_t* labels, int b, int c, int h, int w, float* out);

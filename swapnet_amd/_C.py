@@ -81,6 +81,10 @@ _PROTOS = {
     "swn_pipeline_labels": ([_vp, C.POINTER(_vp)], _i),
     "swn_pipeline_enable_images": ([_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(C.c_uint8), _i, _i], _i),
     "swn_pipeline_images": ([_vp, C.POINTER(_vp), C.POINTER(_i)], _i),
+    "swn_pipeline_enable_png": ([_vp, _i], _i),
+    "swn_pipeline_png": ([_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_size_t), C.POINTER(_i)], _i),
+    "swn_op_png_encode": ([_vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp], _i),
+    "swn_png_stream_bound": ([_i, _i, _i, C.POINTER(C.c_size_t)], _i),
     "swn_op_image_u8": ([_vp, _fp, _i, _i, _i, _i, _vp, _i, _fp, _i, _i, _fp, _i, _vp, _i, _vp], _i),
     "swn_model_set_style_context": ([_vp, _fp, _fp, _i, _i], _i),
     "swn_model_set_gp_random": ([_vp, _fp, _fp], _i),

@@ -532,6 +532,17 @@ int swn_pipeline_images(swn_pipeline* p, uint8_t** dev, int* k) {
     *dev = p->p->images(); *k = Pipeline::IMAGE_SHEETS;
   });
 }
+// (util/util.py:54-69 save_image: the PNG encoding of the sheet, on the device)
+int swn_pipeline_enable_png(swn_pipeline* p, int rows_per_chunk) {
+  return guard([&] { REQUIRE(p, "NULL argument"); p->p->enable_png(rows_per_chunk); });
+}
+int swn_pipeline_png(swn_pipeline* p, uint8_t** streams, uint32_t** sizes, size_t* stride, int* k) {
+  return guard([&] {
+    REQUIRE(p && streams && sizes && stride && k, "NULL argument");
+    REQUIRE(p->p->png_streams(), "swn_pipeline_png: the pipeline was not armed (swn_pipeline_enable_png)");
+    *streams = p->p->png_streams(); *sizes = p->p->png_sizes(); *stride = p->p->png_stride(); *k = Pipeline::IMAGE_SHEETS;
+  });
+}
 int swn_model_forward(swn_model* m, int training, uint64_t seed) {
   return guard([&] { REQUIRE(m, "NULL"); m->m->forward(training != 0, seed); });
 }
@@ -662,6 +673,25 @@ int swn_op_image_u8(swn_ctx* ctx, const float* x, int b, int c, int h, int w, co
     image_u8(tmp.s, a);
     stream_sync(tmp.s);
   });
+}
+// (util/util.py:54-69 save_image: Image.fromarray(a).save(path) -- its filtering and deflate)
+int swn_op_png_encode(swn_ctx* ctx, const uint8_t* img, int n, int h, int w, int rows_per_chunk, uint8_t* streams, size_t stream_stride,
+                      uint32_t* sizes) {
+  return guard([&] {
+    REQUIRE(ctx && img && streams && sizes, "NULL argument");
+    REQUIRE(n > 0, "png_encode: empty batch");
+    const PngGeom g = png_geometry(h, w, rows_per_chunk);
+    REQUIRE(stream_stride >= g.bound, "png_encode: stream_stride is below swn_png_stream_bound");
+    Ctx tmp(ctx->c->s);
+    PngEncodeArgs a;
+    a.img = img; a.n = n; a.h = h; a.w = w; a.rows_per_chunk = rows_per_chunk; a.streams = streams; a.stream_stride = stream_stride; a.sizes = sizes;
+    a.scratch = tmp.alloc(png_scratch_bytes(n, g));
+    png_encode(tmp.s, a);
+    stream_sync(tmp.s);
+  });
+}
+int swn_png_stream_bound(int h, int w, int rows_per_chunk, size_t* out) {
+  return guard([&] { REQUIRE(out, "NULL argument"); *out = png_geometry(h, w, rows_per_chunk).bound; });
 }
 int swn_op_argmax_labels(swn_ctx* ctx, const float* x, int b, int c, int h, int w, int32_t* labels) {
   return guard([&] {

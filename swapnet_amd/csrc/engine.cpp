@@ -1,5 +1,6 @@
 // swapnet_amd -- engine core: arenas, op tape, accumulate planner.
 #include "engine.h"
+#include "png_chunk.h"
 #include <memory>
 
 #include <algorithm>
@@ -2125,6 +2126,32 @@ __attribute__((weak)) void image_u8(Stream&, const ImageU8Args& args) {
         for (int c = 0; c < 3; ++c) a.out[pix * 3 + c] = rgb[c];
       }
   }
+}
+
+// ---- PNG encoding (ops.h png_encode) --------------------------------------------------------------------------------------------------
+// The shapes the encoder takes and the sizes of its buffers: one definition for the launcher, the C interface and the pipeline.
+PngGeom png_geometry(int h, int w, int rows_per_chunk) {
+  if (h < 1 || w < 1) throw Error(1, "png_encode: empty image");
+  if (w > PNG_MAX_WIDTH) throw Error(1, "png_encode: images wider than " + std::to_string(PNG_MAX_WIDTH) + " pixels are refused, got " + std::to_string(w));
+  if (h > (1 << 24)) throw Error(1, "png_encode: images of more than 2^24 rows are refused");
+  if (rows_per_chunk < 0) throw Error(1, "png_encode: rows_per_chunk must be positive, or 0 for the default");
+  const int stride = 1 + 3 * w;
+  PngGeom g;
+  g.R = rows_per_chunk ? rows_per_chunk : std::max(1, std::min(16, PNG_MAX_CHUNK / stride));
+  if ((size_t)g.R * stride > (size_t)PNG_MAX_CHUNK)
+    throw Error(1, "png_encode: a chunk of " + std::to_string(g.R) + " rows of " + std::to_string(stride) + " bytes exceeds " +
+                       std::to_string(PNG_MAX_CHUNK) + " bytes");
+  g.R = std::min(g.R, h);
+  g.chunks = (h + g.R - 1) / g.R;
+  g.chunk_bytes = g.R * stride;
+  g.last_bytes = (h - (g.chunks - 1) * g.R) * stride;
+  g.slot = png_slot_stride((size_t)g.chunk_bytes);
+  g.bound = 2 + (size_t)(g.chunks - 1) * png_chunk_cap((size_t)g.chunk_bytes) + png_chunk_cap((size_t)g.last_bytes) + 4;
+  return g;
+}
+// Weak like the BatchNorm launchers: the device library links png_encode.hip; the host simulator refuses by name.
+__attribute__((weak)) void png_encode(Stream&, const PngEncodeArgs&) {
+  throw Error(1, "png_encode: PNG encoding is not implemented on the host simulator (HIP kernel only)");
 }
 
 }  // namespace swn

@@ -577,9 +577,21 @@ class Pipeline {
   void enable_images(const float body_mean[3], const float body_std[3], const float tex_mean[3], const float tex_std[3],
                      const uint8_t* colours_host, int width, bool reference_quirk);
   uint8_t* images() const { return sheet_; }       // device; NULL until enable_images
+  // The sheet's IMAGE_SHEETS * B images as PNG streams (util/util.py:54-69 save_image's encoding): the two launches of ops.h png_encode
+  // behind the image launches, inside the graph.  Needs enable_images first; allocates the streams, their sizes and the scratch on the
+  // first call, drops a captured graph like enable_images.  Device library only.
+  void enable_png(int rows_per_chunk);
+  uint8_t* png_streams() const { return png_streams_; }      // device [IMAGE_SHEETS * B][png_stride()]; NULL until enable_png
+  uint32_t* png_sizes() const { return png_sizes_; }
+  size_t png_stride() const { return png_stride_; }
  private:
   void enqueue();
   void enqueue_images();
+  uint8_t* png_streams_ = nullptr;
+  uint32_t* png_sizes_ = nullptr;
+  void* png_scratch_ = nullptr;
+  size_t png_stride_ = 0, png_scratch_bytes_ = 0;
+  int png_rows_ = 0;
   uint8_t* sheet_ = nullptr;
   float* minmax_ = nullptr;
   float* rows_ = nullptr;          // [2][B][7]: the body table, then the texture table

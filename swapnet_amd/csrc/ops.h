@@ -674,6 +674,33 @@ inline ImageU8Args image_u8_check(ImageU8Args a) {
   return a;
 }
 
+// ---- PNG encoding of saved images (png_encode.hip, png_chunk.h) --------------------------------------------------------------------
+// What util.save_image (util/util.py:54-69: Image.fromarray(a).save(path)) spends its time on -- PNG row filtering and deflate -- for n
+// interleaved (H,W,3) uint8 images, the layout image_u8 writes: one zlib stream per image (RFC 1950) holding the filtered scanlines;
+// the container around it (signature, IHDR, IDAT, IEND, CRC-32) is a few bytes of host work (util/png.py).  Two launches with fixed
+// grids, nothing the host reads, no allocation: capturable.
+//   chunk kernel, one workgroup per (image, R consecutive rows): adaptive filter per row (all five types, the smallest sum of
+//     min(b, 256 - b) wins, ties to the lower type), run-length matches (distance 1 only, from a parallel scan of the run starts), one
+//     dynamic-Huffman block per chunk, byte-aligned behind it by an empty stored block, or a stored block where that is not larger;
+//   gather kernel, one workgroup per image: 78 01, the chunks back to back, the Adler-32 combined from the chunks' partials.
+// R = rows_per_chunk, 0: min(16, 32768 / (1 + 3W)), at least 1.  W <= 2048 and R * (1 + 3W) <= 32768 (the chunk lives in LDS, its
+// positions in two 64-bit masks per thread, and it fits one stored block); R is cut to H.  HIP kernels only: on the host simulator
+// the launcher throws "not implemented".
+struct PngGeom {
+  int R = 0, chunks = 0, chunk_bytes = 0, last_bytes = 0;    // filtered bytes of a full chunk and of the image's last one
+  size_t slot = 0;                                           // bytes between the chunk slots of the scratch (a multiple of 4)
+  size_t bound = 0;                                          // no stream is longer: 2 + the chunk slots' capacities + 4
+};
+PngGeom png_geometry(int h, int w, int rows_per_chunk);      // throws Error(1, ...) on a shape the encoder refuses
+inline size_t png_scratch_bytes(int n, const PngGeom& g) { return (size_t)n * g.chunks * (g.slot + 3 * sizeof(uint32_t)); }
+struct PngEncodeArgs {
+  const uint8_t* img = nullptr; int n = 0, h = 0, w = 0, rows_per_chunk = 0;
+  void* scratch = nullptr;                                   // device, png_scratch_bytes, 4-byte aligned; nothing of it needs initialising
+  uint8_t* streams = nullptr; size_t stream_stride = 0;      // device [n][stream_stride], stream_stride >= bound
+  uint32_t* sizes = nullptr;                                 // device [n]: bytes of each stream
+};
+void png_encode(Stream& s, const PngEncodeArgs& a);
+
 // ---- losses: each writes the plain MEAN loss into *loss_out (device float) and, if a grad
 // view is given, scale * d(mean loss)/dx into it (scale carries lambda and the 0.5 of loss_D).
 // Views and pad channels (tests/test_loss_ops.py asserts every line of this): the kernels take channel-slice views (cs >= C) and

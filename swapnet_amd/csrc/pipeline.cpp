@@ -83,6 +83,29 @@ void Pipeline::enqueue_images() {
     a.rois = tex_.staged_rois(&a.R); a.colours = colours_; a.width = width_; image_u8(s, a); }
   { ImageU8Args a = base(); a.x = tex_.output_view(); a.C = 3; image_u8(s, a); }                                // fakes
   { ImageU8Args a = base(); a.x = tex_.output_view(); a.C = 3; a.scale_each = 1; a.minmax = minmax_; image_u8(s, a); }   // fakes_scaled
+  if (png_streams_) {
+    PngEncodeArgs a;
+    a.img = sheet_; a.n = IMAGE_SHEETS * B; a.h = warp_.H; a.w = warp_.W; a.rows_per_chunk = png_rows_;
+    a.scratch = png_scratch_; a.streams = png_streams_; a.stream_stride = png_stride_; a.sizes = png_sizes_;
+    png_encode(s, a);
+  }
+}
+
+void Pipeline::enable_png(int rows_per_chunk) {
+  if (!sheet_) throw Error(1, "swn_pipeline_enable_png: the pipeline has no image sheet: call swn_pipeline_enable_images first");
+  if (!is_device_build()) throw Error(1, "swn_pipeline_enable_png: PNG encoding is not implemented on the host simulator (HIP kernel only)");
+  const PngGeom g = png_geometry(warp_.H, warp_.W, rows_per_chunk);
+  const int n = IMAGE_SHEETS * warp_.B;
+  const size_t stride = (g.bound + 15) & ~(size_t)15, scratch = png_scratch_bytes(n, g);
+  Stream& s = ctx_->s;
+  stream_sync(s);                          // a replay in flight uses the buffers and the graph that are about to go
+  graph_destroy(exec_); exec_ = nullptr; warmed_ = false;
+  AllocScope mine(*ctx_, owned_);
+  if (!png_streams_ || stride > png_stride_) png_streams_ = static_cast<uint8_t*>(ctx_->alloc((size_t)n * stride));
+  if (!png_sizes_) png_sizes_ = static_cast<uint32_t*>(ctx_->alloc((size_t)n * sizeof(uint32_t)));
+  if (!png_scratch_ || scratch > png_scratch_bytes_) { png_scratch_ = ctx_->alloc(scratch); png_scratch_bytes_ = scratch; }
+  png_stride_ = std::max(png_stride_, stride);
+  png_rows_ = rows_per_chunk;
 }
 
 void Pipeline::run(bool use_graph) {

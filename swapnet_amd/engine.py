@@ -813,6 +813,35 @@ def op_image_u8(ctx, x=None, labels=None, source=None, rows=None, scale_each=Fal
     return out
 
 
+def png_stream_bound(h, w, rows_per_chunk=0, lib=None):
+    """swn_png_stream_bound: no stream of op_png_encode for this shape is longer.  ValueError for a shape the encoder refuses."""
+    out = C.c_size_t()
+    (lib or _C.lib()).call("swn_png_stream_bound", int(h), int(w), int(rows_per_chunk), C.byref(out))
+    return int(out.value)
+
+
+def op_png_encode(ctx, images, rows_per_chunk=0, out=None):
+    """swn_op_png_encode: the filtering and deflate of util.save_image (util/util.py:54-69) on the device.  images (n,H,W,3) uint8,
+    device or host, tensor or numpy array -> (streams (n, stride) uint8, sizes (n,) int32), both on the context's device: stream i is
+    streams[i, :sizes[i]], a zlib stream of the PNG-filtered scanlines (util/png.py png_container makes the file).  `out`: a
+    contiguous (n, stride >= png_stream_bound) uint8 device tensor to write into; bytes behind a stream are left as they are."""
+    img = _dev(ctx, torch.as_tensor(images), torch.uint8)
+    if img.dim() != 4 or img.shape[3] != 3:
+        raise ValueError("png_encode: images must be (n,H,W,3) uint8, got %s" % (tuple(img.shape),))
+    n, h, w, _ = img.shape
+    bound = png_stream_bound(h, w, rows_per_chunk, lib=ctx.lib)
+    if out is None:
+        out = torch.empty((n, (bound + 15) // 16 * 16), dtype=torch.uint8, device=ctx.device)
+    if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n or out.shape[1] < bound or not out.is_contiguous() \
+            or out.device.type != img.device.type:
+        raise ValueError("png_encode: out must be a contiguous (n, stride >= %d) uint8 tensor on the context's device" % bound)
+    sizes = torch.zeros((n,), dtype=torch.int32, device=ctx.device)
+    if ctx.owns_stream:                     # (the uploads above ran on torch's stream)
+        torch.cuda.current_stream(ctx.device).synchronize()
+    ctx.lib.call("swn_op_png_encode", ctx.handle, _C.ptr(img), n, h, w, int(rows_per_chunk), _C.ptr(out), out.shape[1], _C.ptr(sizes))
+    return out, sizes
+
+
 AMAX_SLOT = 256                     # floats of one amax slot (ops.h)
 EW_ACT_FWD, EW_ACT_BWD, EW_AXPY = 0, 1, 2
 RS_UPSAMPLE_FWD, RS_UPSAMPLE_BWD, RS_MAXPOOL_FWD, RS_MAXPOOL_BWD, RS_REFLECT_FOLD, RS_ACT_PATTERN = 0, 1, 2, 3, 4, 5
@@ -1139,6 +1168,25 @@ class NativePipeline:
         if self.ctx.device.type != "cuda":
             sheet = sheet.copy()
         return OrderedDict(zip(IMAGE_NAMES, sheet))
+
+    def enable_png(self, rows_per_chunk=0):
+        """swn_pipeline_enable_png: from the next run on the sequence also ends with the two PNG launches over the image sheet
+        (inside the captured graph).  Needs enable_images first."""
+        self.lib.call("swn_pipeline_enable_png", self.handle, int(rows_per_chunk))
+
+    def png(self):
+        """The sheet of the last run as PNG files: name -> list of B `bytes` (IMAGE_NAMES order).  Two device-to-host copies (the
+        sizes, then the used part of the streams); the container around each stream is assembled here (util/png.py)."""
+        from .util.png import png_container
+        ps, pz, stride, k = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_int()
+        self.lib.call("swn_pipeline_png", self.handle, C.byref(ps), C.byref(pz), C.byref(stride), C.byref(k))
+        B, H, W = self.warp.B, self.warp.H, self.warp.W
+        n = k.value * B
+        self.ctx.sync()
+        sizes = _wrap_pointer(pz.value, n, self.ctx.device, "<i4").cpu().tolist()
+        used = _wrap_pointer(ps.value, n * stride.value, self.ctx.device, "|u1").reshape(n, stride.value)[:, :max(sizes)].cpu().numpy()
+        files = [png_container(used[i, :sizes[i]].tobytes(), W, H) for i in range(n)]
+        return OrderedDict((name, files[j * B:(j + 1) * B]) for j, name in enumerate(IMAGE_NAMES))
 
     def close(self):
         if getattr(self, "handle", None):

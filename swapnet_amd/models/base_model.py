@@ -102,6 +102,13 @@ class BaseModel(ABC):
         ctx = self.backend.ctx
         return OrderedDict((name, engine.op_image_u8(ctx, **spec).cpu().numpy()) for name, spec in self._image_specs())
 
+    def get_current_pngs(self):
+        """get_current_images() as PNG files, name -> list of B `bytes`: what util.save_image (util/util.py:54-69) would write for
+        each image, encoded on the device (util/png.py encode_png)."""
+        from ..util.png import encode_png
+        ctx = self.backend.ctx
+        return OrderedDict((name, encode_png(ctx, image)) for name, image in self.get_current_images().items())
+
     def _image_specs(self):
         """(visual name, keyword arguments of engine.op_image_u8) in visual_names order."""
         return []

@@ -18,14 +18,16 @@ from .modules.native import NativeBackend
 class TwoStagePipeline:
     def __init__(self, warp_state_dict, texture_state_dict, img_size=128, num_roi=12, ctx=None, lib=None, use_graph=True, images=None):
         """images = dict(body_norm_stats=(mean3, std3), texture_norm_stats=(mean3, std3)[, colours=(num_roi,3) uint8, width_factor=0.01,
-        reference_quirk=True]) arms the image sheet: every call then also leaves the six images inference.py would save, as uint8 on the
-        device inside the same graph; `images()` fetches them."""
+        reference_quirk=True, png=False, png_rows_per_chunk=0]) arms the image sheet: every call then also leaves the six images inference.py
+        would save, as uint8 on the device inside the same graph; `images()` fetches them.  png=True also encodes them as PNG on the
+        device (csrc/png_encode.hip), still inside the graph; `images_png()` fetches the files as bytes."""
         self.ctx = ctx or engine.default_context(lib=lib)
         self.use_graph = use_graph
         self.image_options = dict(images) if images is not None else None
         if self.image_options is not None:
             missing = {"body_norm_stats", "texture_norm_stats"} - set(self.image_options)
-            unknown = set(self.image_options) - {"body_norm_stats", "texture_norm_stats", "colours", "width_factor", "reference_quirk"}
+            unknown = set(self.image_options) - {"body_norm_stats", "texture_norm_stats", "colours", "width_factor", "reference_quirk", "png",
+                                                 "png_rows_per_chunk"}
             if missing or unknown:
                 raise ValueError("images: missing %s, unknown %s" % (sorted(missing), sorted(unknown)))
         self._last = None
@@ -48,6 +50,8 @@ class TwoStagePipeline:
                 colours = o["colours"] if o.get("colours") is not None else BODY_COLORS[:t.num_roi]
                 width = max(1, int(round(o.get("width_factor", 0.01) * W)))
                 self._pipes[key].enable_images(o["body_norm_stats"], o["texture_norm_stats"], colours, width, o.get("reference_quirk", True))
+                if o.get("png"):
+                    self._pipes[key].enable_png(o.get("png_rows_per_chunk", 0))
         return w, t, self._pipes[key]
 
     def images(self):
@@ -60,6 +64,18 @@ class TwoStagePipeline:
         if self._last is None:
             raise ValueError("images(): call the pipeline first")
         out = self._last.images()
+        out["cloths_decoded"] = out["fakes_decoded"]
+        return out
+
+    def images_png(self):
+        """The images of the last call as PNG files, name -> list of B `bytes` under the names of `images()` (cloths_decoded is
+        fakes_decoded's list): what util.save_image would write for each (util/util.py:54-69), filtered and deflated on the device.
+        Pillow opens them to exactly the arrays of `images()`."""
+        if self.image_options is None or not self.image_options.get("png"):
+            raise ValueError("images_png(): the pipeline was built without images=dict(..., png=True)")
+        if self._last is None:
+            raise ValueError("images_png(): call the pipeline first")
+        out = self._last.png()
         out["cloths_decoded"] = out["fakes_decoded"]
         return out
 
