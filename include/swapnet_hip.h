@@ -43,7 +43,8 @@ int swn_abi_version(void);   /* 2: swn_hyper gained d_b1, d_b2; 3: gp_mode, lamb
                                 9: swn_op_norm_act, swn_op_elementwise, swn_op_resample (additions since, version unchanged: swn_op_resize_u8,
                                 swn_model_set_input_texture_sources, swn_op_conv_views, swn_op_chain_resample, swn_op_warp_batch_ex,
                                 swn_model_set_input_warp_batch_ex, swn_op_image_u8, swn_pipeline_enable_images, swn_pipeline_images; the PNG entry points
-                                swn_op_png_encode, swn_png_stream_bound, swn_pipeline_enable_png, swn_pipeline_png were added within ABI 9 as well) */
+                                swn_op_png_encode, swn_png_stream_bound, swn_pipeline_enable_png, swn_pipeline_png were added within ABI 9 as well, and so were
+                                the loss entry points swn_op_ssim, swn_op_charbonnier) */
 const char* swn_last_error(void);
 /* 1 when this library executes on a HIP device (libswapnet_hip.so), 0 for the CI simulator */
 int swn_is_device_build(void);
@@ -634,6 +635,26 @@ int swn_op_loss(swn_ctx* ctx, int kind, const float* a_nchw, const float* b_nchw
 /* bias_grad (the column sums of dy over N*H*W) on a (c + pad_c)-channel buffer whose pads hold 0x7f7f7f7f; c, pad_c % 4 == 0;
  * db = c device floats. */
 int swn_op_bias_grad(swn_ctx* ctx, const float* dy_nchw, int n, int c, int h, int w, int pad_c, float* db);
+/* SSIM(window, reduction, max_val)(img1, img2) of modules/losses/__init__.py:128-259 (Gaussian of :30-35, sigma 1.5), value and both
+ * gradients in one call.  img1, img2: (b,c,h,w) fp32, contiguous NCHW, device.  Zero padding (window - 1) / 2, no renormalisation at
+ * the border; the window is applied separably (rows, then columns), which differs from the reference's 2-D product by rounding only.
+ *   S = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),  C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2
+ *   loss = clamp(1 - S, 0, 1) / 2
+ * loss_map (NULL ok): the per-element loss (reduction 'none').  loss_sum: one device float, the PLAIN sum over all elements ('sum';
+ * 'mean' = loss_sum / (b c h w)), fp64 partials combined in a fixed order: two calls give the same bits.
+ * d1 / d2 (each NULL ok): d loss / d img1, d img2 under the upstream gradient gmap (per element, (b,c,h,w)) or, gmap NULL, the scalar
+ * gscalar (for 'mean' pass g / (b c h w)); torch's convention at the clamp: the gradient passes where 0 <= 1 - S <= 1.  With a
+ * gradient the call runs two tile launches and keeps four coefficient maps (16 bytes per element) in the context's workspace; a
+ * problem beyond the workspace is refused by name.  window: odd, 1 .. 15 (an even one is refused with the reference's message, a
+ * larger one by naming the cap).  Enqueued on the context's stream: no allocation, no synchronisation.  On the simulator all pointers
+ * are host pointers. */
+int swn_op_ssim(swn_ctx* ctx, const float* img1, const float* img2, int b, int c, int h, int w, int window, float max_val,
+                float* loss_map, float* loss_sum, const float* gmap, float gscalar, float* d1, float* d2);
+/* L1_Charbonnier_loss (modules/losses/__init__.py:14-27): loss_sum = sum over n elements of sqrt((x - y)^2 + eps) (device float, fp64
+ * partials, fixed order); dx = gscalar (x - y) / sqrt((x - y)^2 + eps), dy = -dx (each NULL ok).  Any shape of equal numel, contiguous.
+ * One launch plus the finalize, enqueued on the context's stream: no allocation, no synchronisation. */
+int swn_op_charbonnier(swn_ctx* ctx, const float* x, const float* y, size_t n, float eps, float gscalar, float* loss_sum, float* dx,
+                       float* dy);
 /* [InstanceNorm] -> act -> nn.Dropout(p) in TRAINING mode as ONE op (UNetDown / ResidualBlock, modules/layers.py:
  * 18-23,133-136): y, the keep/scale mask it used (0 or 1/(1-p); may be NULL) and, when dy and dx are given, the
  * input gradient computed with the same mask.  NCHW fp32, C % 4 == 0. */

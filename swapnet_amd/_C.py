@@ -135,6 +135,8 @@ _PROTOS = {
     "swn_op_gan_loss": ([_vp, _i, _fp, _i, _i, _i, _i, _f, _i, _f, _fp, _fp], _i),
     "swn_op_loss": ([_vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _fp, _fp, _fp], _i),
     "swn_op_bias_grad": ([_vp, _fp, _i, _i, _i, _i, _i, _fp], _i),
+    "swn_op_ssim": ([_vp, _fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _fp, _f, _fp, _fp], _i),
+    "swn_op_charbonnier": ([_vp, _fp, _fp, C.c_size_t, _f, _f, _fp, _fp, _fp], _i),
     "swn_op_norm_act": ([_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, C.c_uint64, _i, C.c_uint64, _vp, _i, C.POINTER(_i), _i,
                          _fp, _fp, _fp, _fp, _fp, _vp, C.POINTER(_i), _fp, _fp, _fp], _i),
     "swn_op_elementwise": ([_vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_i), _fp, _fp, _fp], _i),

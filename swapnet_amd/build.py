@@ -7,9 +7,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(CSRC, "libswapnet_hip.so")
-HIP_SOURCES = ["device.hip", "conv_gemm.hip", "conv_direct.hip", "conv_ring.hip", "conv_tail.hip", "prof.hip", "wino.hip", "norm_act.hip", "batch_norm.hip", "losses.hip", "optim.hip", "gather.hip", "texture_batch.hip", "warp_batch.hip", "image_resize.hip", "image_out.hip", "png_encode.hip"]
+HIP_SOURCES = ["device.hip", "conv_gemm.hip", "conv_direct.hip", "conv_ring.hip", "conv_tail.hip", "prof.hip", "wino.hip", "norm_act.hip", "batch_norm.hip", "losses.hip", "optim.hip", "gather.hip", "texture_batch.hip", "warp_batch.hip", "image_resize.hip", "image_out.hip", "png_encode.hip", "ssim.hip"]
 CPP_SOURCES = ["engine.cpp", "nets.cpp", "texture.cpp", "pipeline.cpp", "gp.cpp", "capi.cpp"]
-HEADERS = ["common.h", "ops.h", "hip_util.h", "chain_resample.h", "conv_gemm.h", "engine.h", "png_chunk.h", os.path.join("..", "..", "include", "swapnet_hip.h")]
+HEADERS = ["common.h", "ops.h", "hip_util.h", "chain_resample.h", "conv_gemm.h", "engine.h", "png_chunk.h", "ssim_math.h", os.path.join("..", "..", "include", "swapnet_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 
 

@@ -1147,6 +1147,26 @@ int swn_op_bias_grad(swn_ctx* ctx, const float* dy, int n, int c, int h, int w, 
     stream_sync(s);
   });
 }
+// (modules/losses/__init__.py:128-259 SSIM and :14-27 L1_Charbonnier_loss; enqueued only: no allocation, no synchronisation)
+int swn_op_ssim(swn_ctx* ctx, const float* img1, const float* img2, int b, int c, int h, int w, int window, float max_val,
+                float* loss_map, float* loss_sum, const float* gmap, float gscalar, float* d1, float* d2) {
+  return guard([&] {
+    REQUIRE(ctx && img1 && img2 && loss_sum, "NULL argument");
+    SsimArgs a;
+    a.img1 = img1; a.img2 = img2; a.B = b; a.C = c; a.H = h; a.W = w; a.window = window; a.max_val = max_val;
+    a.loss_map = loss_map; a.loss_sum = loss_sum; a.gmap = gmap; a.gscalar = gscalar; a.d1 = d1; a.d2 = d2;
+    ssim_loss(ctx->c->s, a);
+  });
+}
+int swn_op_charbonnier(swn_ctx* ctx, const float* x, const float* y, size_t n, float eps, float gscalar, float* loss_sum, float* dx,
+                       float* dy) {
+  return guard([&] {
+    REQUIRE(ctx && x && y && loss_sum, "NULL argument");
+    CharbonnierArgs a;
+    a.x = x; a.y = y; a.n = n; a.eps = eps; a.gscalar = gscalar; a.loss_sum = loss_sum; a.dx = dx; a.dy = dy;
+    charbonnier_loss(ctx->c->s, a);
+  });
+}
 // ---- the kernels between the convolutions on channel-slice views (swapnet_hip.h: swn_op_norm_act / _elementwise / _resample) ----
 // one operand: an (N,H,W,lead + c + pad) buffer, every byte the sentinel, the logical channels loaded into slice(lead, c)
 struct OpBuf { TView whole, v; };

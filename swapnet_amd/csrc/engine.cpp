@@ -2154,4 +2154,106 @@ __attribute__((weak)) void png_encode(Stream&, const PngEncodeArgs&) {
   throw Error(1, "png_encode: PNG encoding is not implemented on the host simulator (HIP kernel only)");
 }
 
+// ---- SSIM and Charbonnier losses (ops.h ssim_loss / charbonnier_loss) -----------------------------------------------------------------
+// Host forms, weak like texture_batch above: the expressions of ssim_math.h in the order ssim.hip applies them (row pass over the taps
+// in index order, then the column pass; a tap outside the image adds a zero), plane by plane with whole-plane temporaries.
+namespace {
+// out[q] = the zero-padded separable filter of in[q], q < Q planes of H x W
+void ssim_filter_planes(const SsimWindow& win, int ws, int H, int W, int Q, const std::vector<float>* in, std::vector<float>* out) {
+  const int P = ws / 2;
+  std::vector<float> rows((size_t)H * W);
+  for (int q = 0; q < Q; ++q) {
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        float v = 0.f;
+        for (int k = 0; k < ws; ++k) {
+          const int sx = x + k - P;
+          v += win.w[k] * (sx >= 0 && sx < W ? in[q][(size_t)y * W + sx] : 0.f);
+        }
+        rows[(size_t)y * W + x] = v;
+      }
+    out[q].assign((size_t)H * W, 0.f);
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        float v = 0.f;
+        for (int k = 0; k < ws; ++k) {
+          const int sy = y + k - P;
+          v += win.w[k] * (sy >= 0 && sy < H ? rows[(size_t)sy * W + x] : 0.f);
+        }
+        out[q][(size_t)y * W + x] = v;
+      }
+  }
+}
+}  // namespace
+
+__attribute__((weak)) void ssim_loss(Stream&, const SsimArgs& a) {
+  ssim_check(a);
+  const SsimWindow win = ssim_window(a.window);
+  const float C1 = ssim_c1(a.max_val), C2 = ssim_c2(a.max_val);
+  const int H = a.H, W = a.W, P = a.window / 2;
+  const size_t hw = (size_t)H * W;
+  const bool grad = a.d1 || a.d2;
+  double total = 0;
+  std::vector<float> rows[5], mom[5], coef[4], fc[4];
+  for (int plane = 0; plane < a.B * a.C; ++plane) {
+    const float* x = a.img1 + (size_t)plane * hw;
+    const float* y = a.img2 + (size_t)plane * hw;
+    // row pass: the five products enter the filter tap by tap (ssim_tap), as in the kernel
+    for (auto& r : rows) r.assign(hw, 0.f);
+    for (int yy = 0; yy < H; ++yy)
+      for (int xx = 0; xx < W; ++xx) {
+        SsimMoments m = {0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < a.window; ++k) {
+          const int sx = xx + k - P;
+          const bool in = sx >= 0 && sx < W;
+          ssim_tap(m, win.w[k], in ? x[(size_t)yy * W + sx] : 0.f, in ? y[(size_t)yy * W + sx] : 0.f);
+        }
+        const size_t o = (size_t)yy * W + xx;
+        rows[0][o] = m.m1; rows[1][o] = m.m2; rows[2][o] = m.e11; rows[3][o] = m.e22; rows[4][o] = m.e12;
+      }
+    if (grad)
+      for (auto& c : coef) c.assign(hw, 0.f);
+    for (int yy = 0; yy < H; ++yy)
+      for (int xx = 0; xx < W; ++xx) {
+        float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < a.window; ++k) {
+          const int sy = yy + k - P;
+          for (int q = 0; q < 5; ++q) v[q] += win.w[k] * (sy >= 0 && sy < H ? rows[q][(size_t)sy * W + xx] : 0.f);
+        }
+        const size_t o = (size_t)yy * W + xx;
+        const SsimMoments m = {v[0], v[1], v[2], v[3], v[4]};
+        const SsimTerms st = ssim_terms(m, C1, C2);
+        const float l = ssim_loss_of(st.S);
+        total += (double)l;
+        if (a.loss_map) a.loss_map[(size_t)plane * hw + o] = l;
+        if (grad) {
+          const SsimCoefs c = ssim_coefs(m, st, a.gmap ? a.gmap[(size_t)plane * hw + o] : a.gscalar);
+          coef[0][o] = c.a1; coef[1][o] = c.a2; coef[2][o] = c.b; coef[3][o] = c.c;
+        }
+      }
+    if (grad) {
+      ssim_filter_planes(win, a.window, H, W, 4, coef, fc);
+      for (size_t o = 0; o < hw; ++o) {
+        const float xv = x[o], yv = y[o];
+        if (a.d1) a.d1[(size_t)plane * hw + o] = fc[0][o] + 2.f * xv * fc[2][o] + yv * fc[3][o];
+        if (a.d2) a.d2[(size_t)plane * hw + o] = fc[1][o] + 2.f * yv * fc[2][o] + xv * fc[3][o];
+      }
+    }
+  }
+  a.loss_sum[0] = (float)total;
+}
+
+__attribute__((weak)) void charbonnier_loss(Stream&, const CharbonnierArgs& a) {
+  if (!a.x || !a.y || !a.loss_sum) throw Error(1, "charbonnier: NULL argument");
+  if (a.n < 1) throw Error(1, "charbonnier: empty input");
+  double total = 0;
+  for (size_t i = 0; i < a.n; ++i) {
+    float gr;
+    total += (double)charbonnier_term(a.x[i], a.y[i], a.eps, a.gscalar, &gr);
+    if (a.dx) a.dx[i] = gr;
+    if (a.dy) a.dy[i] = -gr;
+  }
+  a.loss_sum[0] = (float)total;
+}
+
 }  // namespace swn

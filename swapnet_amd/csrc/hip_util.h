@@ -24,6 +24,10 @@ inline void check_launch(const char* what) {
   if (e != hipSuccess) throw Error(2, std::string("kernel launch failed (") + what + "): " + hipGetErrorString(e));
 }
 
+// out[0] = (float)(mul * sum of partial[0 .. n)), one 64-lane block adding in a fixed order (losses.hip: the finalize of every loss
+// reduction; ssim.hip uses it too)
+void finalize_sum(Stream& s, const double* partial, int n, double mul, float* out);
+
 // ---- slot audit (ops.h slot_audit; conv_ring.hip) -- called by the launchers only while slot_audit_on() ----------------------
 // `slot` against the amax of the operand the launch gathers ([batch][rows][C] floats, row stride rs, batch stride bs): throws
 // unless amax <= max(slot) and, for amax > 0, max(slot) <= 4096 * amax (tests/hostsim/hostsim_ops.cpp sim_slot_check).  Synchronises.

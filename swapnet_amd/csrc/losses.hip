@@ -463,6 +463,10 @@ void gan_loss(Stream& s, const TView& pred, float label, float scale, float* los
 
 }  // namespace
 
+void finalize_sum(Stream& s, const double* partial, int n, double mul, float* out) {
+  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(64), 0, hs(s), partial, n, mul, out);
+}
+
 void bce_logits_loss(Stream& s, const TView& pred, float label, float scale, float* loss_out, const TView* dpred, const float* label_dev) {
   gan_loss<0>(s, pred, label, scale, loss_out, dpred, label_dev);
 }

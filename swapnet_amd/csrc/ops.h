@@ -1,12 +1,13 @@
 // swapnet_amd -- device op launchers.  The engine (engine.cpp) is written against this
 // header only.  The product implementation is the set of HIP translation units in this
 // directory (conv_gemm.hip and the kernel-family units behind it, wino.hip, norm_act.hip, batch_norm.hip, losses.hip, optim.hip, gather.hip,
-// texture_batch.hip, warp_batch.hip, image_resize.hip, image_out.hip).
+// texture_batch.hip, warp_batch.hip, image_resize.hip, image_out.hip, ssim.hip).
 // tests/hostsim/hostsim_ops.cpp implements the same signatures with plain loops so that
 // the engine's graph / backward / packing logic can be checked in CI without a GPU; it is
 // never part of the shipped library.
 #pragma once
 #include "common.h"
+#include "ssim_math.h"
 #include <cmath>
 #include <cstdlib>
 #include <functional>
@@ -762,6 +763,47 @@ void norm_act_bwd2(Stream& s, const NormActBwd2Args& a);
 
 // out[0] = a[0]*ca + b[0]*cb (device scalars; used to combine loss terms without a sync)
 void scalar_axpby(Stream& s, const float* a, float ca, const float* b, float cb, float* out);
+
+// ---- SSIM and Charbonnier losses of modules.losses (ssim.hip, ssim_math.h) -------------------------------------------------------
+// SSIM(window, reduction, max_val)(img1, img2) of modules/losses/__init__.py:128-259 on contiguous NCHW fp32 planes (the op is
+// depthwise: each of the B*C planes on its own, no NHWC conversion): zero padding (window - 1) / 2, the float32 Gaussian of sigma
+// 1.5 applied separably (rows, then columns: the reference's 2-D window up to rounding), loss = clamp(1 - S, 0, 1) / 2 (ssim_math.h
+// has the arithmetic).  One fused launch plus the fixed-order finalize: a workgroup owns a 32 x 32 tile of one plane, stages the
+// tile and its halo of both images in LDS with zeros outside the image, and no filtered map touches HBM.
+//   loss_map (optional): the per-element loss, (B,C,H,W);  loss_sum: device float, the PLAIN sum over B*C*H*W (fp64 block partials of
+//   fp32 terms combined in a fixed order: two runs give bit-equal results).
+// Backward, when d1 or d2 is given: the upstream gradient is gmap (per element, reduction 'none') or, gmap NULL, the scalar gscalar
+// (for 'mean' the caller passes g / numel).  The forward launch also leaves the four coefficient maps a1, a2, b, c of ssim_math.h in
+// the stream's workspace, and a second launch filters them: d1 = f(a1) + 2 x f(b) + y f(c), d2 = f(a2) + 2 y f(b) + x f(c).
+// The workspace must hold 4 * B*C*H*W floats plus one double per tile; a larger problem is refused by name.  window: odd, 1 ..
+// SSIM_MAX_WINDOW.  Enqueued on s: no allocation, no synchronisation.
+struct SsimArgs {
+  const float* img1 = nullptr; const float* img2 = nullptr;
+  int B = 0, C = 0, H = 0, W = 0, window = 0; float max_val = 1.f;
+  float* loss_map = nullptr; float* loss_sum = nullptr;
+  const float* gmap = nullptr; float gscalar = 0.f;
+  float* d1 = nullptr; float* d2 = nullptr;
+};
+constexpr int SSIM_TILE = 32;
+void ssim_loss(Stream& s, const SsimArgs& a);
+// the argument checks of every ssim_loss implementation (the HIP launcher and the host loop of engine.cpp)
+inline void ssim_check(const SsimArgs& a) {
+  if (!a.img1 || !a.img2 || !a.loss_sum) throw Error(1, "ssim: NULL argument");
+  if (a.B < 1 || a.C < 1 || a.H < 1 || a.W < 1) throw Error(1, "ssim: empty sizes");
+  if (a.window < 1 || a.window % 2 == 0)
+    throw Error(1, "ssim: kernel_size must be an odd positive integer. Got " + std::to_string(a.window));
+  if (a.window > SSIM_MAX_WINDOW)
+    throw Error(1, "ssim: windows larger than " + std::to_string(SSIM_MAX_WINDOW) + " are not implemented, got " + std::to_string(a.window));
+  const size_t tiles = (size_t)ceil_div(a.H, SSIM_TILE) * ceil_div(a.W, SSIM_TILE) * a.B * a.C;
+  if (tiles > 0x7fffffffull) throw Error(1, "ssim: more than 2^31 - 1 tiles");
+}
+// L1_Charbonnier_loss (modules/losses/__init__.py:14-27): loss_sum = sum sqrt((x - y)^2 + eps) over n elements of any shape, one
+// launch plus the finalize, fp64 partials; dx = gscalar (x - y) / sqrt((x - y)^2 + eps), dy = -dx (each optional).
+struct CharbonnierArgs {
+  const float* x = nullptr; const float* y = nullptr; size_t n = 0; float eps = 1e-6f, gscalar = 0.f;
+  float* loss_sum = nullptr; float* dx = nullptr; float* dy = nullptr;
+};
+void charbonnier_loss(Stream& s, const CharbonnierArgs& a);
 
 // ---- optimizer / parameter layout ------------------------------------------------------
 struct AdamWArgs {

@@ -662,6 +662,60 @@ def op_bias_grad(ctx, dy, pad_c=0):
     return db
 
 
+SSIM_MAX_WINDOW = 15                # ssim_math.h: odd windows 1 .. 15 have a kernel
+
+
+def _torch_stream_done(ctx):
+    """A context with a stream of its own: what torch enqueued for the operands (uploads, the producer's kernels) has finished."""
+    if ctx.owns_stream:
+        torch.cuda.current_stream(ctx.device).synchronize()
+
+
+def op_ssim(ctx, img1, img2, window, max_val=1.0, want_map=False, grad=None, want_grad=(False, False)):
+    """swn_op_ssim: the SSIM loss of modules.losses (reference modules/losses/__init__.py:128-259) on (B,C,H,W) float32 operands.
+    Returns (loss_sum[1] = the plain sum over all elements, loss_map or None, d1 or None, d2 or None).  `grad`: the upstream
+    gradient, a (B,C,H,W) tensor (reduction 'none') or a Python scalar; want_grad = which of the two image gradients to compute."""
+    a, b = _dev(ctx, img1), _dev(ctx, img2)
+    if a.dim() != 4 or a.shape != b.shape:
+        raise ValueError("ssim: two (B,C,H,W) tensors of one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    n, c, h, w = a.shape
+    total = torch.empty(1, dtype=torch.float32, device=ctx.device)
+    lmap = torch.empty_like(a) if want_map else None
+    d1 = torch.empty_like(a) if want_grad[0] else None
+    d2 = torch.empty_like(a) if want_grad[1] else None
+    gmap, gscalar = None, 0.0
+    if d1 is not None or d2 is not None:
+        if torch.is_tensor(grad) and grad.dim() > 0:
+            gmap = _dev(ctx, grad)
+            if gmap.shape != a.shape:
+                raise ValueError("ssim: the upstream gradient map must have the images' shape")
+        else:
+            gscalar = float(grad)
+    _torch_stream_done(ctx)
+    ctx.lib.call("swn_op_ssim", ctx.handle, _C.ptr(a), _C.ptr(b), n, c, h, w, int(window), C.c_float(max_val), _C.ptr(lmap), _C.ptr(total),
+                 _C.ptr(gmap), C.c_float(gscalar), _C.ptr(d1), _C.ptr(d2))
+    if ctx.owns_stream:                     # (the caller reads the results on torch's stream)
+        ctx.sync()
+    return total, lmap, d1, d2
+
+
+def op_charbonnier(ctx, x, y, eps=1e-6, grad=None, want_grad=(False, False)):
+    """swn_op_charbonnier: L1_Charbonnier_loss (reference modules/losses/__init__.py:14-27), sum sqrt((x - y)^2 + eps) over tensors of
+    equal numel.  Returns (loss_sum[1], dx or None, dy or None); `grad`: the upstream scalar."""
+    a, b = _dev(ctx, x), _dev(ctx, y)
+    if a.numel() != b.numel() or a.numel() == 0:
+        raise ValueError("charbonnier: two non-empty tensors of equal numel, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    total = torch.empty(1, dtype=torch.float32, device=ctx.device)
+    dx = torch.empty_like(a) if want_grad[0] else None
+    dy = torch.empty_like(b) if want_grad[1] else None
+    _torch_stream_done(ctx)
+    ctx.lib.call("swn_op_charbonnier", ctx.handle, _C.ptr(a), _C.ptr(b), C.c_size_t(a.numel()), C.c_float(eps),
+                 C.c_float(float(grad) if grad is not None else 0.0), _C.ptr(total), _C.ptr(dx), _C.ptr(dy))
+    if ctx.owns_stream:
+        ctx.sync()
+    return total, dx, dy
+
+
 def op_texture_batch(ctx, textures_u8, labels_u8, rois_raw, sample_params, mean, std, x_min, y_min, height, width, cloth_channels=19):
     """TextureDataset.__getitem__ for a batch through swn_op_texture_batch: (input_textures, target_textures, cloths, rois) on the
     context's device, NCHW float32 / (B,R,4), from uint8 HWC images (B,Hs,Ws,3), uint8 label maps (B,Hl,Wl), raw ROIs (B,R,4) and

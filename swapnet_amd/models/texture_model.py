@@ -3,6 +3,7 @@
 lambda_l1 * L1 + lambda_content * content + lambda_style * style."""
 from argparse import ArgumentParser
 
+from .. import engine
 from ..modules.losses import PerceptualLoss
 from ..modules.swapnet_modules import TextureModule
 from ..util.decode_labels import decode_cloth_labels, labels_to_onehot
@@ -23,10 +24,17 @@ class TextureModel(BaseGAN):
             parser.add_argument("--lambda_style", type=float, default=1e-8, help="weight for content loss in final term")
             parser.add_argument("--vgg_weights", default=None, help="(swapnet_amd) file with torchvision vgg16 weights "
                                 "(vgg16().state_dict() or .features.state_dict()) for the perceptual loss")
+            parser.add_argument("--monitor_ssim", type=int, default=0, metavar="WINDOW",
+                                help="(swapnet_amd) report the mean SSIM loss of the fakes against the targets as loss 'ssim', "
+                                "under an odd WINDOW x WINDOW Gaussian (e.g. 11); evaluated when the losses are read, "
+                                "never on the step path; 0 = off")
             parser.set_defaults(display_ncols=5)
         return parser
 
     def __init__(self, opt):
+        monitor = int(getattr(opt, "monitor_ssim", 0) or 0)           # (refused before any network is built)
+        if monitor and (monitor < 1 or monitor % 2 == 0 or monitor > engine.SSIM_MAX_WINDOW):
+            raise ValueError("--monitor_ssim takes an odd window from 1 to %d, got %d" % (engine.SSIM_MAX_WINDOW, monitor))
         super().__init__(opt)
         self.visual_names = ["textures_unnormalized", "cloths_decoded", "fakes", "fakes_scaled"]
         if self.is_train:
@@ -42,6 +50,19 @@ class TextureModel(BaseGAN):
             for loss in ["l1", "content", "style"]:
                 if getattr(opt, "lambda_" + loss) != 0:
                     self.loss_names.append(f"G_{loss}")
+            self.monitor_ssim = monitor
+            if self.monitor_ssim:
+                self.loss_names.append("ssim")
+                self.loss_ssim = 0.0
+
+    def get_current_losses(self):
+        """--monitor_ssim: the reconstruction-quality number is computed here, when the losses are read (one kernel per print
+        interval): SSIM(window, 'mean', max_val=2.0) of the tensors the L1 term compares; 2.0 = the tanh range."""
+        if self.is_train and getattr(self, "monitor_ssim", 0) and self._native() is not None and self.targets is not None:
+            fakes, targets = self.fakes, self.targets
+            total, _, _, _ = engine.op_ssim(self.backend.ctx, fakes, targets, self.monitor_ssim, max_val=2.0)
+            self.loss_ssim = float(total[0]) / fakes.numel()
+        return super().get_current_losses()
 
     def _init_vgg(self):
         """The reference's PerceptualLoss builds torchvision's vgg16(pretrained=True) (perceptual.py:26).  Sources
